@@ -18,7 +18,18 @@ position in the counter-based generator); for the single-series workloads the sa
 times the STRONG split of BASELINE config 2 (4096 restarts / N per rank) and reports it in
 "strong_scaling".  cfg4 / cfg5 are fixed grids -> "strong" by construction.
 
-Prints ONE JSON line on rank 0; see the task contract for the fields.  Extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one
+timed step), steps, warmup, config.  A plain run does only what
+the headline needs: set up, warm up, time --steps steps, write the outputs of the last timed step
+(--dump-outputs DIR), print the line.  --full adds the objects below (and, for N > 1, the
+strong-scaling run); --no-verify / --no-host-entry / --no-cpu-baseline drop single legs of it.
+  --dump-outputs DIR   theta.npy [cells, 6+p+q], lik.npy, n_iter.npy, status.npy [cells] of the last
+                timed launch, float64 (n_iter / status are exact small integers), rank 0's cells;
+                rank r > 0 writes <name>_rank<r>.npy.  Above 64 MB in all, a fixed seeded sample of
+                cells is written instead, with its cell indices in sample_index.npy.  The inputs are
+                a function of the arguments alone (ldsr_amd/synth.py is seeded), so two builds can
+                be compared output for output.
+Objects of --full:
   roofline      the binding resource is fp64 VALU issue, not HBM: achieved = algorithmic flops
                 ((6p+6q+50)*T per unit) / EM-kernel time measured with HIP events
                 on the launch stream, against the 78.6 TFLOP/s fp64 vector peak.  The nominal HBM
@@ -280,6 +291,80 @@ def host_entry_rate(L, job, T, p, q, niter, tol, algo, units_rank, steps=10, war
             "bytes_out": int(th.nbytes + lik.nbytes + nit.nbytes + st.nbytes)}
 
 
+def roofline(workload, mask, kernel_name, niter, tol, T, p, q, units_rank, kern_ms):
+    """--full: the roofline object of the timed launches (kern_ms = their mean HIP-event kernel time)."""
+    kern_s = kern_ms * 1e-3
+    fpu, bpu = flops_per_unit(T, p, q), bytes_per_unit(T, p, q)
+    tflops = fpu * units_rank / kern_s / 1e12             # this GPU's kernel
+    logical_gbs = bpu * units_rank / kern_s / 1e9
+    pmc, stale = load_pmc(workload, mask, kernel_name, niter, tol)
+    roof = {"bound": "fp64_valu", "achieved": tflops, "peak": FP64_VALU_PEAK_TFLOPS,
+            "unit": "TFLOP/s", "frac": tflops / FP64_VALU_PEAK_TFLOPS,
+            "traffic": None, "kernel": kernel_name, "kernel_ms": kern_ms,
+            "algorithmic_flops_per_unit": fpu, "units_per_launch": units_rank,
+            "hbm_logical_bytes_per_unit": bpu, "hbm_logical_gbs": logical_gbs,
+            "hbm_logical_frac": logical_gbs / HBM_PEAK_GBS, "hbm_peak_gbs": HBM_PEAK_GBS,
+            "flops_are": "reference-equivalent: what src/EM.cpp spends on these units, (6p+6q+50) T "
+                         "each; kernels with a closed-form lead or steady-state sweeps execute "
+                         "fewer -- fp64_executed_frac is what the SQ counters saw",
+            "note": "fp64 VALU issue is the binding resource; hbm_logical_* is BASELINE.json's "
+                    "nominal byte figure (not traffic: the series is served from LDS, the "
+                    "filtered states never leave registers) and may exceed 1; traffic / "
+                    "hbm_measured_* / issue_frac are rocprofv3 PMC numbers of the committed "
+                    "passes named in pmc_source"}
+    if pmc is not None:
+        roof["traffic"] = pmc.get("hbm_bytes_per_launch")
+        roof["pmc_source"] = pmc.get("source")
+        roof["pmc_stale"] = bool(stale)
+        if pmc.get("hbm_bytes_per_launch") is not None:
+            roof["hbm_measured_gbs"] = pmc["hbm_bytes_per_launch"] / kern_s / 1e9
+            roof["hbm_measured_frac"] = roof["hbm_measured_gbs"] / HBM_PEAK_GBS
+        if pmc.get("valu_insts_per_unit") is not None:
+            # wave-instructions issued per second against 1024 SIMDs x one fp64 issue / 4 clk
+            roof["valu_insts_per_unit"] = pmc["valu_insts_per_unit"]
+            roof["issue_frac"] = (pmc["valu_insts_per_unit"] * units_rank / kern_s
+                                  / (N_SIMD * CLOCK_HZ / 4.0))
+        if pmc.get("fp64_flops_executed_per_unit"):
+            # what the kernel actually executes (FMA = 2 flops, counted by the SQ): the
+            # parallel-in-time formulation does ~1.9x the algorithmic flops
+            roof["fp64_executed_tflops"] = pmc["fp64_flops_executed_per_unit"] * units_rank / kern_s / 1e12
+            roof["fp64_executed_frac"] = roof["fp64_executed_tflops"] / FP64_VALU_PEAK_TFLOPS
+        if pmc.get("valu_active_per_wave_cycle") is not None:
+            roof["valu_busy_frac"] = 2.0 * pmc["valu_active_per_wave_cycle"]   # two waves per SIMD
+        if pmc.get("sustained_clock_ghz"):
+            # `peak` assumes the 2.4 GHz boost clock; under fp64 load the chip holds less
+            # (GRBM_GUI_ACTIVE / 8 XCDs / kernel duration of the committed PMC pass): the same
+            # achieved rate against the peak AT THAT CLOCK separates clock from code
+            clk = pmc["sustained_clock_ghz"]
+            roof["sustained_clock_ghz"] = clk
+            roof["peak_at_sustained_clock"] = FP64_VALU_PEAK_TFLOPS * clk / (CLOCK_HZ / 1e9)
+            roof["frac_at_sustained_clock"] = tflops / roof["peak_at_sustained_clock"]
+    return roof
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(job, out_dir, rank, world, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: what the caller of ldsr_em_batch_device_lead receives from the last timed
+    launch (theta, lik, n_iter, status of every cell of this rank), as float64 .npy files.  Past
+    the cap (shared over the ranks) a fixed seeded sample of cells, indices in sample_index.npy."""
+    arrays = {"theta": job.d_th.cpu().numpy(), "lik": job.d_lik.cpu().numpy(),
+              "n_iter": job.d_nit.cpu().numpy(), "status": job.d_st.cpu().numpy()}
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    n = job.cells
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    keep = (cap_bytes // world) // max(row_bytes + 8, 1)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(12345).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` invoked plainly: start the N ranks as a CHILD
     `python -m torch.distributed.run` (this parent never imports torch or touches the GPU, and
@@ -362,12 +447,20 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="headline split of a single-series workload over the ranks (default weak: "
                          "the per-GPU configuration of BASELINE.json; strong: its restarts / N)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline: roofline (HIP-event kernel time, committed "
+                         "PMC figures), the oracle check of the last timed launch, host_entry, "
+                         "cpu_baseline and, for N > 1, the strong-scaling run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed launch's theta / lik / n_iter / status as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
     ap.add_argument("--no-host-entry", action="store_true",
-                    help="skip the host-pointer-entry leg (ldsr_em_batch, PCIe-inclusive; reported beside value)")
+                    help="--full without the host-pointer-entry leg (ldsr_em_batch, PCIe-inclusive; reported beside value)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle check of a 64-cell sample of the last timed launch")
+                    help="--full without the oracle check of a 64-cell sample of the last timed launch")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -459,13 +552,15 @@ def main():
         dist.all_gather(parts, mine)
         return [int(x.item()) for x in parts]
 
-    dt, units_rank, units_all, kern_ms = timed(job, True)
+    dt, units_rank, units_all, kern_ms = timed(job, args.full)   # HIP-event kernel times: --full only
+    if args.dump_outputs:
+        dump_outputs(job, args.dump_outputs, rank, world)
     per_rank = units_by_rank(units_rank)
     if L.ldsr_last_em_kernel(local_rank, name_buf, 160) == 0:      # the kernel the timed launches ran
         kernel_name = name_buf.value.decode()
 
     strong = None
-    if world > 1 and single and scaling == "weak":
+    if args.full and world > 1 and single and scaling == "weak":
         # the same run, BASELINE config 2 as ONE job split N ways (restarts / N per rank)
         sjob = Job(L, torch, dev, local_rank,
                    build_problem(args.workload, args.mask, world, rank, "strong"), T, p, q, niter,
@@ -477,52 +572,6 @@ def main():
 
     if rank == 0:
         value = units_all * args.steps / dt
-        kern_s = kern_ms * 1e-3
-        fpu, bpu = flops_per_unit(T, p, q), bytes_per_unit(T, p, q)
-        tflops = fpu * units_rank / kern_s / 1e12             # this GPU's kernel
-        logical_gbs = bpu * units_rank / kern_s / 1e9
-        pmc, stale = load_pmc(args.workload, args.mask, kernel_name, niter, args.tol)
-        roof = {"bound": "fp64_valu", "achieved": tflops, "peak": FP64_VALU_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": tflops / FP64_VALU_PEAK_TFLOPS,
-                "traffic": None, "kernel": kernel_name, "kernel_ms": kern_ms,
-                "algorithmic_flops_per_unit": fpu, "units_per_launch": units_rank,
-                "hbm_logical_bytes_per_unit": bpu, "hbm_logical_gbs": logical_gbs,
-                "hbm_logical_frac": logical_gbs / HBM_PEAK_GBS, "hbm_peak_gbs": HBM_PEAK_GBS,
-                "flops_are": "reference-equivalent: what src/EM.cpp spends on these units, (6p+6q+50) T "
-                             "each; kernels with a closed-form lead or steady-state sweeps execute "
-                             "fewer -- fp64_executed_frac is what the SQ counters saw",
-                "note": "fp64 VALU issue is the binding resource; hbm_logical_* is BASELINE.json's "
-                        "nominal byte figure (not traffic: the series is served from LDS, the "
-                        "filtered states never leave registers) and may exceed 1; traffic / "
-                        "hbm_measured_* / issue_frac are rocprofv3 PMC numbers of the committed "
-                        "passes named in pmc_source"}
-        if pmc is not None:
-            roof["traffic"] = pmc.get("hbm_bytes_per_launch")
-            roof["pmc_source"] = pmc.get("source")
-            roof["pmc_stale"] = bool(stale)
-            if pmc.get("hbm_bytes_per_launch") is not None:
-                roof["hbm_measured_gbs"] = pmc["hbm_bytes_per_launch"] / kern_s / 1e9
-                roof["hbm_measured_frac"] = roof["hbm_measured_gbs"] / HBM_PEAK_GBS
-            if pmc.get("valu_insts_per_unit") is not None:
-                # wave-instructions issued per second against 1024 SIMDs x one fp64 issue / 4 clk
-                roof["valu_insts_per_unit"] = pmc["valu_insts_per_unit"]
-                roof["issue_frac"] = (pmc["valu_insts_per_unit"] * units_rank / kern_s
-                                      / (N_SIMD * CLOCK_HZ / 4.0))
-            if pmc.get("fp64_flops_executed_per_unit"):
-                # what the kernel actually executes (FMA = 2 flops, counted by the SQ): the
-                # parallel-in-time formulation does ~1.9x the algorithmic flops
-                roof["fp64_executed_tflops"] = pmc["fp64_flops_executed_per_unit"] * units_rank / kern_s / 1e12
-                roof["fp64_executed_frac"] = roof["fp64_executed_tflops"] / FP64_VALU_PEAK_TFLOPS
-            if pmc.get("valu_active_per_wave_cycle") is not None:
-                roof["valu_busy_frac"] = 2.0 * pmc["valu_active_per_wave_cycle"]   # two waves per SIMD
-            if pmc.get("sustained_clock_ghz"):
-                # `peak` assumes the 2.4 GHz boost clock; under fp64 load the chip holds less
-                # (GRBM_GUI_ACTIVE / 8 XCDs / kernel duration of the committed PMC pass): the same
-                # achieved rate against the peak AT THAT CLOCK separates clock from code
-                clk = pmc["sustained_clock_ghz"]
-                roof["sustained_clock_ghz"] = clk
-                roof["peak_at_sustained_clock"] = FP64_VALU_PEAK_TFLOPS * clk / (CLOCK_HZ / 1e9)
-                roof["frac_at_sustained_clock"] = tflops / roof["peak_at_sustained_clock"]
         out = {
             "metric": "restart x EM-iteration / s (T=%d, p=%d, q=%d)" % (T, p, q),
             "value": value, "unit": "restart*EM-iter/s", "n_gpus": world, "steps": args.steps,
@@ -539,20 +588,22 @@ def main():
                        "sharding": "rank r = the r-th of %d parts of every series' restarts, no collective" % world,
                        "units_per_rank": per_rank,
                        "imbalance_max_over_mean": max(per_rank) * len(per_rank) / max(sum(per_rank), 1)},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roofline(args.workload, args.mask, kernel_name, niter, args.tol,
+                                       T, p, q, units_rank, kern_ms)
         if strong is not None:
             out["strong_scaling"] = strong
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             out["verified"] = verify_sample(job, p, q, niter, args.tol)
             if not out["verified"]["ok"]:
                 print(json.dumps(out), flush=True)
                 sys.exit("bench.py: the timed launch does not match the CPU oracle")
-        if world == 1 and not args.no_host_entry:
+        if args.full and world == 1 and not args.no_host_entry:
             he = host_entry_rate(L, job, T, p, q, niter, args.tol, args.algo, units_rank)
             he["vs_device_resident"] = he["value"] / (units_rank * args.steps / dt)
             out["host_entry"] = he
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             Y, U, V = (job.d_y.cpu().numpy(), job.d_u.cpu().numpy(), job.d_v.cpu().numpy())
             out["cpu_baseline"] = cpu_baseline(p, q, niter, Y, U, V, seed=1)
             out["cpu_baseline"]["rscript_reference"] = rscript_reference_probe(T, p, q, niter)

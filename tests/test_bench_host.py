@@ -152,3 +152,56 @@ def test_host_entry_leg_builds_the_call_it_times(monkeypatch):
     assert seen["S"] == 48 and seen["T"] == 813 and seen["niter"] == 7 and seen["off"] == [int(x) for x in off]
     assert r["units_per_call"] == th0.shape[0] * 7 and r["same_units_as_device_entry"] is True
     assert r["value"] > 0 and r["bytes_in"] == Y.nbytes + U.nbytes + V.nbytes + th0.nbytes
+
+
+class _Host:
+    """A host array standing in for a device tensor (.cpu().numpy())."""
+
+    def __init__(self, a):
+        self.a = a
+
+    def cpu(self):
+        return self
+
+    def numpy(self):
+        return self.a
+
+
+def _fake_job(cells, P):
+    import types
+    rng = np.random.default_rng(5)
+    return types.SimpleNamespace(cells=cells, d_th=_Host(rng.standard_normal((cells, P))),
+                                 d_lik=_Host(rng.standard_normal(cells)),
+                                 d_nit=_Host(np.full(cells, 100, np.int32)),
+                                 d_st=_Host(np.zeros(cells, np.int32)))
+
+
+def test_dump_outputs_writes_what_the_launch_returned(tmp_path):
+    """--dump-outputs: theta / lik / n_iter / status of every cell of the last launch, float64,
+    exactly the values the device buffers held."""
+    import bench
+    job = _fake_job(4096, 9)
+    bench.dump_outputs(job, str(tmp_path), 0, 1)
+    assert sorted(os.listdir(tmp_path)) == ["lik.npy", "n_iter.npy", "status.npy", "theta.npy"]
+    for name, src in (("theta", job.d_th.a), ("lik", job.d_lik.a), ("n_iter", job.d_nit.a), ("status", job.d_st.a)):
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, src), name
+    bench.dump_outputs(job, str(tmp_path / "r"), 3, 4)
+    assert "theta_rank3.npy" in os.listdir(tmp_path / "r")
+
+
+def test_dump_outputs_samples_a_fixed_subset_past_the_cap(tmp_path):
+    """Past the 64 MB cap a seeded sample of cells is written, the same one run after run, with
+    the cell indices beside it."""
+    import bench
+    job = _fake_job(5000, 9)
+    cap = 1000 * (9 + 3 + 1) * 8
+    bench.dump_outputs(job, str(tmp_path / "a"), 0, 1, cap_bytes=cap)
+    bench.dump_outputs(job, str(tmp_path / "b"), 0, 1, cap_bytes=cap)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= cap + 5 * 128                                  # + the .npy headers
+    idx = np.load(tmp_path / "a" / "sample_index.npy").astype(np.int64)
+    assert idx.size == 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "theta.npy"), job.d_th.a[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "lik.npy"), job.d_lik.a[idx])

@@ -108,3 +108,37 @@ def test_bench_launch_matches_oracle(mask):
     # ... and the bench's own 64-cell check of that launch agrees
     v = bench.verify_sample(job, p, q, niter, 0.0)
     assert v["ok"] and v["cells"] == 64 and v["n_iter_equal"]
+
+
+def test_plain_bench_run_dumps_the_last_timed_launch(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline fields for exactly K
+    timed steps, none of the --full legs, and the outputs of the last timed launch as float64 .npy
+    files -- every cell of config 2, a sample of them checked against the CPU oracle."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from oracle import oracle as O
+
+    out = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=bench.ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "restart*EM-iter/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["config"]["units_per_step"] == 4096 * 100
+    assert not {"roofline", "verified", "host_entry", "cpu_baseline", "strong_scaling"} & set(line)
+
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in ("theta", "lik", "n_iter", "status")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert d["theta"].shape == (4096, 9) and d["lik"].shape == d["n_iter"].shape == d["status"].shape == (4096,)
+    assert np.all(d["n_iter"] == 100) and np.all(d["status"] == 0)
+    Y, U, V, shared, off, th0, n = bench.build_problem("cfg2", "dense", 1, 0)
+    idx = np.linspace(0, n - 1, 32).astype(np.int64)
+    ref_th, ref_lik, ref_it, _ = O.em_batch(Y, U, V, np.zeros(idx.size, np.int32), th0[idx], 100, 0.0, n_threads=16)
+    assert np.array_equal(d["n_iter"][idx], ref_it)
+    assert parity_close(d["lik"][idx], ref_lik, RTOL, ATOL)
+    assert parity_close(d["theta"][idx], ref_th, RTOL, ATOL)

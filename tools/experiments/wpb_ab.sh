@@ -1,5 +1,5 @@
 # same-box A/B of the pair family's waves per workgroup (LDSR_PAIR_WPB: 8 = one workgroup per CU as before, unset = two of four where the LDS allows, 2 = four of two)
-run() { python bench.py --steps 8 --warmup 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(\"$TAG\", d[\"roofline\"][\"kernel\"], \"%.4f ms kernel  %.4g units/s\" % (d[\"roofline\"][\"kernel_ms\"], d[\"value\"]))"; }
+run() { python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(\"$TAG\", d[\"roofline\"][\"kernel\"], \"%.4f ms kernel  %.4g units/s\" % (d[\"roofline\"][\"kernel_ms\"], d[\"value\"]))"; }
 for w in 8 4 2; do
   export LDSR_PAIR_WPB=$w
   for wl in cfg4 cfg5 cfg2; do TAG="$wl wpb=$w"; run --workload $wl; done

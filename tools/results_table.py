@@ -33,7 +33,7 @@ def line_of(path):
 def table(rnd):
     prof = os.path.join(ROOT, "profiles")
     pmc = {e["workload"]: e for e in json.load(open(os.path.join(prof, "pmc_summary.json")))["entries"] if e["round"] == rnd}
-    out = ["Round %s, one MI355X, `python bench.py --workload W` (niter = 100, tol = 0, fully observed series for cfg2 / cfg3, the "
+    out = ["Round %s, one MI355X, `python bench.py --full --workload W` (niter = 100, tol = 0, fully observed series for cfg2 / cfg3, the "
            "configs' own masks for cfg4 / cfg5; boxes differ by ±4 %%).  Sources: `profiles/%s_cfgN_bench.json` (value, HIP-event kernel time, "
            "fractions), `profiles/%s_cfgN_kernel_stats.csv` (rocprofv3 average), `profiles/pmc_summary.json` (counters, clock).\n" % (rnd, rnd, rnd),
            "| workload | kernel | restart×EM-iter/s (whole job) | EM kernel ms: HIP events / rocprofv3 | `roofline.frac` | at sustained clock (GHz) | executed fp64 ÷ peak | VALU instr. per unit | HBM MB per launch (PMC, upper bound) |",
@@ -51,7 +51,7 @@ def table(rnd):
             e.get("valu_insts_per_unit", float("nan")), e.get("hbm_bytes_per_launch", float("nan")) / 1e6))
         if w == "cfg2":
             host, cpu = d.get("host_entry"), d.get("cpu_baseline")
-            full = os.path.join(prof, "%s_cfg2_full_bench.json" % rnd)       # the driver's default invocation
+            full = os.path.join(prof, "%s_cfg2_full_bench.json" % rnd)       # the complete line, cpu_baseline included
             if os.path.exists(full):
                 cpu = line_of(full).get("cpu_baseline") or cpu
     out.append("")
