@@ -172,12 +172,14 @@ int ldsr_em_batch_device(int device, void *stream, int n_series, int T, int p, i
                          size_t workspace_bytes);
 
 /* Which kernel a call with these arguments launches: writes its name as rocprofv3 prints it
- * (e.g. "em_pair_kernel<1, 2, 32, false>") into buf and returns the resolved algorithm
- * (LDSR_ALGO_SERIAL / LDSR_ALGO_SCAN / LDSR_ALGO_PAIR), or a negative value for unsupported arguments.
- * With LDSR_ALGO_AUTO it assumes a launch large enough to fill the device (below ~3600 cells the
- * entries keep the scan kernel, whose four-cell workgroups spread over more CUs), and with tol > 0
- * it reports what ldsr_em_batch_device runs (the scan kernel); the host-pointer entries additionally
- * take the pair kernel when every series is fully observed. */
+ * (e.g. "em_pair_kernel<1, 2, 32, 32, false, false>") into buf and returns the resolved algorithm
+ * (LDSR_ALGO_SERIAL / LDSR_ALGO_SCAN / LDSR_ALGO_PAIR / LDSR_ALGO_QUAD), or a negative value for
+ * unsupported arguments.  With LDSR_ALGO_AUTO it assumes a launch large enough to fill the device
+ * (smaller launches keep the scan kernel, whose smaller workgroups spread over more CUs; how many cells
+ * fill the device depends on the shape, tol and the lead -- ldsr_last_em_kernel tells what a launch
+ * ran), and with tol > 0 it reports what ldsr_em_batch_device runs (the scan kernel, except for short
+ * series); the host-pointer entries additionally take the pair family when every series is fully
+ * observed (ldsr_em_plan_lead with lead_steps = -1). */
 int ldsr_em_plan(int T, int p, int q, int niter, double tol, int algo, char *buf, size_t len);
 
 /* The same two with one more piece of knowledge about the data: the first lead_steps time steps of

@@ -379,9 +379,10 @@ struct Carver {
     }
 };
 
-// ---- algorithm choice / workspace layout -------------------------------------------------------
-// compute units of a device (cached)
+// ---- workspace layout (which kernel runs: em_plan.hip) ------------------------------------------
+// compute units of a device (cached; a bad device id fails at hipSetDevice)
 static int device_cu_count(int device) {
+    if (device < 0) return 256;
     static std::mutex mu;
     static std::vector<int> cache;
     std::lock_guard<std::mutex> lk(mu);
@@ -392,14 +393,6 @@ static int device_cu_count(int device) {
         cache[(size_t)device] = n;
     }
     return cache[(size_t)device];
-}
-
-// LDSR_PAIR=0 in the environment keeps AUTO off the two-cells-per-wave kernel (same-box A/B runs)
-// LDSR_FORCE_FILL=1: AUTO treats every launch as large enough for the pair family (tests and the
-// fuzzer exercise AUTO's choices with a handful of cells)
-static bool force_fill() {
-    static const bool on = [] { const char *e = getenv("LDSR_FORCE_FILL"); return e && e[0] == '1'; }();
-    return on;
 }
 
 // name of the EM kernel of the most recent launch per device (ldsr_last_em_kernel)
@@ -418,58 +411,12 @@ extern "C" int ldsr_last_em_kernel(int device, char *buf, size_t len) {
     return 0;
 }
 
-// LDSR_LEAD=0 keeps AUTO off the closed-form lead of the pair family (same-box A/B runs)
-static bool lead_enabled() {
-    static const bool on = [] { const char *e = getenv("LDSR_LEAD"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// LDSR_STEADY_ORDER=0: the steady form takes the cells in the caller's order (A/B runs)
-static bool order_enabled() {
-    static const bool on = [] { const char *e = getenv("LDSR_STEADY_ORDER"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-static bool pair_enabled() {
-    static const bool on = [] { const char *e = getenv("LDSR_PAIR"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// AUTO resolves to LDSR_ALGO_PAIR as the name of the several-cells-per-wave family (two or four
-// cells per wave); which member -- or the scan kernel after all -- runs is decided per launch
-// (em_batch_device_impl: launch size, tol, fully observed or not).
-static int resolve_algo(int algo, int T, int PP, int QQ) {
-    if (algo == LDSR_ALGO_AUTO) {
-        if (pair_enabled() && (em_pair_supported(T, PP, QQ, 32) || em_pair_supported(T, PP, QQ, 16)))
-            return LDSR_ALGO_PAIR;
-        return em_scan_supported(T, PP, QQ) ? LDSR_ALGO_SCAN : LDSR_ALGO_SERIAL;
-    }
-    return algo;
-}
-
-// cells per workgroup of the EM launch (the workspace's block table is sized for the scan
-// kernel's value, the smallest of them, whenever its image is built)
-static int cells_per_block(int algo, int T, int PP, int QQ, int lpc = 32, int lead = 0) {
-    if (algo == LDSR_ALGO_PAIR || algo == LDSR_ALGO_QUAD) {
-        if (algo == LDSR_ALGO_QUAD) lpc = 16;
-        const int c = em_pair_cells_per_block(T, PP, QQ, lpc, lead);
-        return c > 0 ? c : 16;
-    }
-    return algo == LDSR_ALGO_SCAN ? em_scan_cells_per_block(T, PP, QQ) : 64;
-}
-
 struct WsLayout {
     size_t sc, yp, yz, up, vp, img, img2, img3, blk, soc, queue, perm, perm_key, scratch, total;
     long scratch_stride, img_stride;   // img_stride: doubles per series image (0 = no image)
     long img2_stride;                  // pair kernel's image (0 = none)
     long img3_stride;                  // ... and its lead image
-    int max_blocks, img_L, img_NL, img2_L, img2_NL = 32, lead = 0;
-    // cell order of the pair kernel's steady form (series_prep orders when order_on): set per launch
-    bool order_on = false;
-    bool build_scan_img = true;        // false: a pair-family launch with no smoother pass behind it
-    int order_cpb = 0, order_ntr = 0;
-    const double *order_theta0 = nullptr;
-    const int *order_off = nullptr;     // device copy of the cell offsets (behind the block table)
+    int max_blocks, img_L, img_NL;
 };
 
 static WsLayout ws_layout(int n_series, int T, int PP, int QQ, int shared_uv, int n_cells,
@@ -488,7 +435,7 @@ static WsLayout ws_layout(int n_series, int T, int PP, int QQ, int shared_uv, in
     L.img = o; o = align256(o + sizeof(double) * (size_t)L.img_stride * n_series);
     // room for the pair family's images whatever runs in the end (the launch decides: member,
     // chunk length, a closed-form lead): the largest 32-lane image, and u_t of a lead of up to T steps
-    L.img2_stride = 0; L.img2_L = 0; L.img3_stride = 0;
+    L.img2_stride = 0; L.img3_stride = 0;
     if (PP <= 8 && QQ <= 8 && algo != LDSR_ALGO_SERIAL) {
         // (wide inputs: the LEAD form's tail only, chunks of <= 16 steps)
         L.img2_stride = pair_image_doubles(PP <= 4 && QQ <= 4 ? 32 : 16, PP, QQ, 32);
@@ -537,90 +484,29 @@ static int check_em(int niter, double tol) {
 
 extern "C" size_t ldsr_em_workspace_bytes(int n_series, int T, int p, int q, int n_cells,
                                           int algo) {
-    if (n_series < 1 || T < 2 || p < 1 || q < 1 || p > LDSR_MAXPQ || q > LDSR_MAXPQ || n_cells < 0)
-        return 0;
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
-    const int algo_in = algo;
-    algo = resolve_algo(algo, T, PP, QQ);
-    if (algo == LDSR_ALGO_SCAN && !em_scan_supported(T, PP, QQ)) return 0;
-    if (algo == LDSR_ALGO_PAIR && !em_pair_supported(T, PP, QQ, 32) && !(algo_in == LDSR_ALGO_AUTO && em_pair_supported(T, PP, QQ, 16))) return 0;
-    if (algo == LDSR_ALGO_QUAD && !em_pair_supported(T, PP, QQ, 16)) return 0;
+    if (n_series < 1 || n_cells < 0) return 0;
+    EmPlanIn in;
+    in.T = T; in.p = p; in.q = q; in.niter = 2; in.algo = algo;
+    const EmPlan pl = em_plan(in);
+    if (!pl.ok) return 0;
     // the layout for shared_uv = 0 is an upper bound for shared_uv = 1
-    return ws_layout(n_series, T, PP, QQ, 0, n_cells, algo, cells_per_block(algo, T, PP, QQ)).total;
+    return ws_layout(n_series, T, pl.PP, pl.QQ, 0, n_cells, pl.algo_layout, pl.layout_cpb).total;
 }
 
-// scan kernel: cells converge at their own pace (tol > 0) -> per-series work queue
-static bool scan_uses_queue(int T, int PP, int QQ, double tol) {
-    return tol > 0.0 || em_scan_queue_only(T, PP, QQ);
-}
-
-// the tail [T - tail, T) AUTO sweeps when the first lead_steps steps of every series are missing
-// (0: no closed-form lead) -- the same rule as em_batch_device_impl
-// early stopping on series that may have missing steps: does the two-cells-per-wave kernel still
-// beat the scan kernel?  (measured: only in four-wave workgroups with chunks of <= 13 steps)
-static bool pair_pays_with_early_stopping(int T, int PP, int QQ) {
-    return T <= 416 && em_pair_waves_per_block(T, PP, QQ, 32, 0) == 4;
-}
-
-// Runs to convergence on fully observed series with wide-ish inputs (padded p + q >= 8): since the scan kernel reads its
-// image ahead (round 4) it beats the two-cells-per-wave kernel on long chunks (T = 813 (3,3) 20 000 cells 2.46 against
-// 2.79 ms), and four cells per wave lose to two (T = 260 (4,4) 20 000 cells 1.13 against 0.97): tools/auto_regret.py,
-// profiles/r04_auto_regret.txt.
-static bool conv_wide(double tol, int PP, int QQ) { return tol > 0.0 && PP + QQ >= 8; }
-
-// does the LEAD form at lp lanes per cell fit a CU's LDS: the tail's image, the strips and the lead's u_t
-static bool lead_fits(int T, int tail, int PP, int QQ, int lp) {
-    const bool wide = PP > 4 || QQ > 4;
-    int Lc = 0;
-    long img = 0;
-    em_pair_layout(tail, PP, QQ, lp, &Lc, &img, true);
-    if (!img) return false;
-    const size_t lds = ((size_t)img + (wide ? 4 : 8) * (size_t)pair_strip_doubles(Lc) +
-                        (size_t)pair_lead_doubles(T - tail, lp, PP)) * sizeof(double);
-    return lds <= 160 * 1024;
-}
-// four cells per wave for the tail of a lead: narrow inputs, tails of <= 256 steps (p = 3, 4 since the
-// lead's second pass sums 5 + 2 p values instead of 7 + 4 p: they fit the 16-lane reduction now)
-static bool lead_quad(int T, int tail, int PP, int QQ) {
-    return PP <= 8 && QQ <= 8 && tail <= 256 && em_pair_supported(tail, PP, QQ, 16, true) && lead_fits(T, tail, PP, QQ, 16);
-}
-
-static bool lead_short34(int T, int tail, int PP) { return PP > 2 && T - tail < 512; }
-
-static int lead_tail(int T, int PP, int QQ, int lead_steps) {
-    if (!pair_enabled() || !lead_enabled() || lead_steps < 192 || PP > 8 || QQ > 8) return 0;
-    const bool wide = PP > 4 || QQ > 4;     // (two cells per wave, LEAD form only: kernels_scan.hip pair_plan)
-    int tail = std::max(T - lead_steps, 80);
-    tail = (tail + 15) / 16 * 16;
-    static const int max_tail = [] { const char *e = getenv("LDSR_LEAD_MAX_TAIL"); return e ? atoi(e) : 512; }();
-    if (tail > max_tail || tail > 512 || T - tail < 128) return 0;
-    // p = 3, 4 have the two-cells-per-wave LEAD form only (7 + 4 p lead sums per step): on short
-    // series the four-cells-per-wave kernel over all T steps is quicker (tools/auto_regret.py, same
-    // box: T = 260 (4,4) 20 000 cells 1.86 ms against 1.29, to convergence 11.4 against 7.0; the Nakhon
-    // Phanom shape, T = 813 with a lead of 733 steps, keeps it: 3.29 -> 2.50 ms)
-    // (with four cells per wave -- p = 3, 4 since round 3, launches of >= 3/4 of a round -- the lead pays on
-    // short series too: the caller checks lead_short34() before it falls back to two cells per wave)
-    if (PP > 2 && T - tail < 512 && !lead_quad(T, tail, PP, QQ)) return 0;
-    // the lead's u_t live in LDS behind the tail's image and the strips
-    (void)wide;
-    if (lead_quad(T, tail, PP, QQ)) return tail;
-    // (padded p = 8 up to T = 1024: four cells per wave or the scan kernel, see em_batch_device_impl)
-    return ((PP < 8 || T > 1024) && lead_fits(T, tail, PP, QQ, 32)) ? tail : 0;
-}
-
-static int em_plan_impl(int T, int p, int q, int niter, double tol, int algo, char *buf, size_t len,
-                        bool fully_observed);
-
+// what a launch that fills the device runs (lead_steps: -1 fully observed, 0 unknown, > 0 common lead)
 extern "C" int ldsr_em_plan_lead(int T, int p, int q, int niter, double tol, int algo, int lead_steps,
                                  char *buf, size_t len) {
-    if (T < 2 || p < 1 || q < 1 || p > LDSR_MAXPQ || q > LDSR_MAXPQ || niter < 2 || !(tol >= 0.0))
-        return -1;
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
-    const int tail = algo == LDSR_ALGO_AUTO ? lead_tail(T, PP, QQ, lead_steps) : 0;
-    if (!tail) return em_plan_impl(T, p, q, niter, tol, algo, buf, len, lead_steps < 0);
-    const int lpc = lead_quad(T, tail, PP, QQ) ? 16 : 32;
-    if (buf && len) em_pair_kernel_name(tail, PP, QQ, lpc, tol > 0.0 || PP > 4 || QQ > 4, buf, len, true);
-    return lpc == 16 ? LDSR_ALGO_QUAD : LDSR_ALGO_PAIR;
+    EmPlanIn in;
+    in.T = T; in.p = p; in.q = q; in.niter = niter; in.tol = tol; in.algo = algo; in.lead_steps = lead_steps;
+    const EmPlan pl = em_plan(in);
+    if (!pl.ok) return -1;
+    if (buf && len) em_plan_kernel_name(pl, buf, len);
+    return pl.algo;
+}
+
+extern "C" int ldsr_em_plan(int T, int p, int q, int niter, double tol, int algo, char *buf,
+                            size_t len) {
+    return ldsr_em_plan_lead(T, p, q, niter, tol, algo, 0, buf, len);
 }
 
 // the kernel one Kalman_smoother pass of this shape runs (launch_smoother): the FIT form of the scan
@@ -643,45 +529,13 @@ extern "C" size_t ldsr_kernel_inventory(char *buf, size_t len) {
     return s.size() + 1;
 }
 
-extern "C" int ldsr_em_plan(int T, int p, int q, int niter, double tol, int algo, char *buf,
-                            size_t len) {
-    return em_plan_impl(T, p, q, niter, tol, algo, buf, len, false);
-}
-
-static int em_plan_impl(int T, int p, int q, int niter, double tol, int algo, char *buf, size_t len,
-                        bool fully_observed) {
-    if (T < 2 || p < 1 || q < 1 || p > LDSR_MAXPQ || q > LDSR_MAXPQ || niter < 2 || !(tol >= 0.0))
-        return -1;
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
-    const bool was_auto = algo == LDSR_ALGO_AUTO;
-    algo = resolve_algo(algo, T, PP, QQ);
-    // what ldsr_em_batch_device runs (the host-pointer entries additionally take the pair / quad
-    // kernels with tol > 0 when every series is fully observed)
-    const bool masked_conv = was_auto && algo == LDSR_ALGO_PAIR && tol > 0.0 && !fully_observed;
-    if (masked_conv && !pair_pays_with_early_stopping(T, PP, QQ)) algo = LDSR_ALGO_SCAN;
-    if (was_auto && algo == LDSR_ALGO_PAIR && conv_wide(tol, PP, QQ) && T > 512 && em_scan_supported(T, PP, QQ)) algo = LDSR_ALGO_SCAN;
-    if (algo == LDSR_ALGO_SCAN) {
-        if (!em_scan_supported(T, PP, QQ)) return -1;
-        if (buf && len) em_scan_kernel_name(T, PP, QQ, scan_uses_queue(T, PP, QQ, tol), false, buf, len);
-    } else if (algo == LDSR_ALGO_PAIR || algo == LDSR_ALGO_QUAD) {
-        // AUTO (a launch that fills the device assumed): four cells per wave where they fit, else two
-        int lpc = algo == LDSR_ALGO_QUAD ? 16 : 32;
-        if (was_auto && !conv_wide(tol, PP, QQ) && em_pair_supported(T, PP, QQ, 16)) { lpc = 16; algo = LDSR_ALGO_QUAD; }
-        if (!em_pair_supported(T, PP, QQ, lpc)) return -1;
-        if (buf && len) em_pair_kernel_name(T, PP, QQ, lpc, tol > 0.0, buf, len);
-    } else if (algo == LDSR_ALGO_SERIAL) {
-        if (buf && len) em_serial_kernel_name(T, PP, QQ, buf, len);
-    } else {
-        return -1;
-    }
-    return algo;
-}
-
-// Runs series_prep on `stream` and fills the workspace pointers.
-static int prepare_series(hipStream_t stream, int n_series, int T, int p, int q, int PP, int QQ,
-                          const double *d_y, const double *d_u, const double *d_v, int shared_uv,
-                          char *ws, const WsLayout &L) {
+// series_prep's parameters for the prepared series and, with scan_img, the scan kernel's image (an EM
+// launch of the pair family adds its images and the steady form's cell order)
+static PrepParams prep_params(int n_series, int T, int p, int q, int PP, int QQ, const double *d_y,
+                              const double *d_u, const double *d_v, int shared_uv, char *ws,
+                              const WsLayout &L, bool scan_img) {
     PrepParams pp;
+    memset(&pp, 0, sizeof(pp));
     pp.T = T; pp.p = p; pp.q = q; pp.PP = PP; pp.QQ = QQ; pp.shared_uv = shared_uv;
     pp.y = d_y; pp.u = d_u; pp.v = d_v;
     pp.yp = (double *)(ws + L.yp);
@@ -690,228 +544,121 @@ static int prepare_series(hipStream_t stream, int n_series, int T, int p, int q,
     pp.vp = (double *)(ws + L.vp);
     pp.sc = (SeriesConst *)(ws + L.sc);
     pp.queue = (int *)(ws + L.queue);
-    pp.img = (L.img_stride && L.build_scan_img) ? (double *)(ws + L.img) : nullptr;
+    pp.img = (L.img_stride && scan_img) ? (double *)(ws + L.img) : nullptr;
     pp.img_stride = L.img_stride;
     pp.L = L.img_L;
     pp.NL = L.img_NL;
-    pp.img2 = L.img2_stride ? (double *)(ws + L.img2) : nullptr;
-    pp.img2_stride = L.img2_stride;
-    pp.L2 = L.img2_L;
-    pp.NL2 = L.img2_NL;
-    pp.lead = L.lead;
-    pp.img3 = (L.lead > 0 && L.img3_stride) ? (double *)(ws + L.img3) : nullptr;
-    pp.img3_stride = L.img3_stride;
     pp.n_series = n_series;
-    pp.perm = L.order_on ? (int *)(ws + L.perm) : nullptr;
-    pp.perm_key = (int *)(ws + L.perm_key);
-    pp.cell_off = L.order_off;
-    pp.theta0 = L.order_theta0;
-    pp.order_cpb = L.order_cpb;
-    pp.order_ntr = L.order_ntr;
-    HIPCHK(launch_series_prep(pp, n_series, stream));
-    return LDSR_OK;
+    return pp;
 }
 
-// liks_nanfill: entries of d_liks beyond a cell's n_iter are set to NaN (the ABI contract of the
-// batch entry points); the restart-grid path reads only the first n_iter entries and skips it.
-static int em_batch_device_impl(int device, hipStream_t stream, int n_series, int T, int p, int q,
-                                const double *d_y, const double *d_u, const double *d_v,
-                                int shared_uv, const int *cell_offsets, const double *d_theta0,
-                                int niter, double tol, int algo, double *d_theta, double *d_lik,
-                                int *d_n_iter, int *d_status, double *d_liks, int liks_nanfill,
-                                void *d_workspace, size_t workspace_bytes,
-                                const int *abort_flag = nullptr, int dense_hint = -1,
-                                int *algo_used = nullptr, int lead_hint = -1, int *lead_used = nullptr,
-                                int lead_force = 0, const int *plan_off = nullptr, int plan_ns = 0,
-                                bool fit_follows = true) {
-    int rc = check_common(n_series, T, p, q, d_y, cell_offsets);
+// One EM launch on device data (cell_offsets: a host array).  em_batch_device_impl fills in the plan it
+// chose and the workspace layout it carved.
+struct EmLaunch {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int n_series = 0, T = 0, p = 0, q = 0, shared_uv = 0, niter = 0, algo = LDSR_ALGO_AUTO;
+    double tol = 0.0;
+    const double *y = nullptr, *u = nullptr, *v = nullptr, *theta0 = nullptr;
+    const int *cell_offsets = nullptr;
+    double *theta = nullptr, *lik = nullptr, *liks = nullptr;
+    int *n_iter = nullptr, *status = nullptr;
+    int liks_nanfill = 1;           // liks beyond a cell's n_iter set to NaN (the batch ABI; the restart grid reads n_iter)
+    void *workspace = nullptr;
+    size_t workspace_bytes = 0;
+    const int *abort_flag = nullptr;
+    int lead_steps = 0, lead_force = 0;     // EmPlanIn's data facts and forced lead
+    const int *plan_off = nullptr;  // the whole call's offsets (plan_ns series; null: cell_offsets): AUTO's kernel,
+    int plan_ns = 0;                // hence the rounding of the results, must not depend on how many devices share it
+    bool fit_follows = true;        // the winners' FIT pass follows: series_prep builds the scan kernel's image even
+                                    // behind a pair-family launch (the bare device entries skip it: 4096 values at config 2)
+    EmPlan plan;                    // out
+    WsLayout layout;                // out
+};
+
+static int em_batch_device_impl(EmLaunch &E) {
+    const int n_series = E.n_series, T = E.T, p = E.p, q = E.q;
+    const int *cell_offsets = E.cell_offsets;
+    int rc = check_common(n_series, T, p, q, E.y, cell_offsets);
     if (rc) return rc;
-    rc = check_em(niter, tol);
+    rc = check_em(E.niter, E.tol);
     if (rc) return rc;
-    if (!d_theta0 || !d_theta || !d_lik || !d_n_iter || !d_status || !d_workspace)
+    if (!E.theta0 || !E.theta || !E.lik || !E.n_iter || !E.status || !E.workspace)
         return fail(LDSR_EINVAL, "NULL output / workspace pointer");
     const int n_cells = cell_offsets[n_series];
     if (n_cells == 0) return LDSR_OK;
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
-    const bool was_auto = algo == LDSR_ALGO_AUTO;
-    algo = resolve_algo(algo, T, PP, QQ);
-    const int algo_layout = algo;       // what the workspace was sized and laid out for
-    // Is the launch large enough for the pair family to pay?  Counted in CUs' worth of cells (eight
-    // waves).  Eight-wave workgroups (long chunks): >= 7/8 of the CUs.  Four-wave
-    // workgroups (short series, two per CU): the shared per-wave work pays much earlier --
-    // same box, T = 400 (1,2) / 200 (2,2) / 300 (1,4), scan -> pair -> quad in ms: 1024 cells
-    // 0.47 -> 0.39 -> 0.54, 2048 0.50 -> 0.42 -> 0.57, 3072 0.74 -> 0.62 -> 0.59, 4096 0.94 -> 0.68 ->
-    // 0.62 (tools/fill_ab.sh) -- two cells per wave from 1/4 of the CUs (1024 cells), four from 3/8
-    // (3072 cells).
-    auto fills = [&](int Te, int lp, bool lead_form = false) {
-        if (!em_pair_supported(Te, PP, QQ, lp, lead_form)) return false;
-        const int c = (64 / lp) * 8;          // a CU's eight waves
-        long wgs = 0;
-        // (a slice of a multi-device call counts the whole call's cells: plan_off)
-        const int *po = plan_off ? plan_off : cell_offsets;
-        const int pn = plan_off ? plan_ns : n_series;
-        for (int s = 0; s < pn; s++) wgs += (po[s + 1] - po[s] + c - 1) / c;
-        const long cus = device_cu_count(device);
-        if (force_fill()) return true;
-        // (runs to convergence: only up to chunks of 13 steps -- beyond, the scan kernel with its read-ahead wins on
-        // launches of this size: T = 600 (1,2) 2000 cells 0.284 against 0.313 ms, (2,4) 0.384 against 0.512)
-        if (!lead_form && em_pair_waves_per_block(Te, PP, QQ, lp, 0) == 4 && (tol == 0.0 || Te <= 416))
-            return wgs * 8 >= (lp == 16 ? 3 : 2) * cus;
-        // the closed-form lead skips most of the work, so it pays from ~1536 cells (same box, scan ->
-        // LEAD in ms, tools/lead_fill_ab.sh: T = 2000 (1,4) 1536 cells 1.94 -> 1.40, 3072 3.79 -> 1.47;
-        // T = 4000 (2,2) 1536 cells 8.27 -> 2.47; T = 813 (3,3) 1536 0.92 -> 0.85, 3072 1.42 -> 1.27);
-        // with early stopping only for long leads (2048 cells: T = 2000 2.81 -> 2.23, T = 813 2.85 -> 3.09)
-        // from T = 1536 on the scan kernel's chunks are 28..32 steps long (and its image may live in global
-        // memory): there the lead pays whatever the launch size -- 50 lone cells, niter = 200, scan -> LEAD in
-        // ms: T = 2000 (1,4) 3.61 -> 2.44, (3,5) 17.1 -> 3.96, T = 4000 (2,2) 6.30 -> 4.95; at T = 1100..1300
-        // it is a toss-up (1.40 -> 1.48, 1.81 -> 2.07, 2.17 -> 1.78)
-        // (four cells per wave with p = 3, 4 or wide inputs -- possible since the lead's second pass sums
-        // 5 + 2 p values -- pay from 3072 cells, with leads of 1024 steps and more from 6144: same box, two ->
-        // four cells per wave in ms, T = 813 (3,3) 8192 cells 2.33 -> 1.55, 4096 1.24 -> 1.06, 3072 1.21 -> 1.03,
-        // 2048 0.82 -> 0.98; (4,8) T = 1024 3072 cells 1.52 -> 1.26, 2048 1.06 -> 1.22; T = 2000 (3,4) 4096
-        // cells 2.25 -> 2.64, 6144 4.33 -> 2.73)
-        if (lead_form && lp == 16 && (PP > 2 || QQ > 4)) return wgs * (lead_hint >= 1024 ? 4 : 8) >= 3 * cus;
-        if (lead_form && T >= 1536) return true;
-        if (lead_form && (tol == 0.0 || lead_hint >= 1024))
-            return wgs * (lp == 16 ? 16 : 8) >= 3 * cus;
-        return wgs * 8 >= 7 * cus;
-    };
-    // A long all-missing lead common to every series (paleo-type data; lead_hint from the caller
-    // that has seen y): the pair family's LEAD form handles it in closed form and sweeps only the
-    // tail -- [T - tail, T) with tail a multiple of 16 of at most 512 steps (chunks of <= 16 steps:
-    // four cells per wave up to 256 steps, two beyond).
-    int lead = 0, lpc = algo == LDSR_ALGO_QUAD ? 16 : 32;
-    if (was_auto && algo != LDSR_ALGO_SERIAL) {
-        const int tail = lead_tail(T, PP, QQ, lead_hint);
-        if (tail) {
-            if (lead_quad(T, tail, PP, QQ) && fills(tail, 16, true)) { lead = T - tail; lpc = 16; algo = LDSR_ALGO_QUAD; }
-            // (two cells per wave with padded p = 8 run ONE four-wave workgroup per CU and lose to the scan kernel:
-            // T = 813 (7,7) 2048 cells 1.76 against 1.40 ms, 4096 cells 3.03 against 2.66, four per wave 1.89)
-            // (beyond T = 1024 the scan kernel's chunks are long and they win again)
-            else if ((PP < 8 || T > 1024) && !lead_short34(T, tail, PP) && fills(tail, 32, true)) { lead = T - tail; lpc = 32; algo = LDSR_ALGO_PAIR; }
-        }
-    }
-    if (lead_force > 0 && (algo == LDSR_ALGO_PAIR || algo == LDSR_ALGO_QUAD)) lead = lead_force;   // (a re-run of part of a batch)
-    if (lead_used) *lead_used = lead;
-    const int Te = T - lead;            // steps the sweeps of the pair family work on
-    if (!lead) {
-        // AUTO with early stopping: the pair kernel couples two cells per wave and sixteen per
-        // workgroup (= per CU), so widely different iteration counts cost it more than they cost the
-        // scan kernel's four-cell workgroups.  Measured (converged runs, tol = 1e-5): fully observed
-        // series (cells stop after 28..63 iterations) pair +8..12 %; masked series (4..176, cfg5 up
-        // to 745 iterations) pair -2..-24 %.  So with tol > 0 AUTO takes the pair kernel only for
-        // series known to be fully observed (the host-pointer entries look; dense_hint).
-        // (Short series are the exception: in the two-cells-per-wave kernel's four-wave workgroups --
-        // chunks of <= 13 steps -- the coupling costs less than the shared per-wave work saves:
-        // T = 300 (2,2) +34 %, T = 400 (1,2) +11..33 %; from T = 500 on the scan kernel wins by 5..24 %.)
-        const bool masked_conv = was_auto && algo == LDSR_ALGO_PAIR && tol > 0.0 && dense_hint != 1;
-        if (masked_conv && !pair_pays_with_early_stopping(T, PP, QQ)) algo = LDSR_ALGO_SCAN;
-        if (was_auto && algo == LDSR_ALGO_PAIR && conv_wide(tol, PP, QQ) && T > 512 && em_scan_supported(T, PP, QQ)) algo = LDSR_ALGO_SCAN;
-        // ... and only when its workgroups (one per CU: 16 cells at two cells per wave, 32 at four) fill
-        // the device: 512 cells are 32 pair workgroups on 32 of 256 CUs but 128 scan workgroups on 128
-        // of them (a quarter of the time).  Four cells per wave where they fit and fill, else two.
-        if (was_auto && algo == LDSR_ALGO_PAIR) {
-            // (masked series with early stopping reach this point only as short series: there four
-            // cells per wave win once the launch is large -- tools/auto_regret.py, 20 000 cells:
-            // T = 260 (4,4) 9.5 -> 7.0 ms, T = 150 (1,2) 2.96 -> 2.74; at 2000 cells two per wave stay ahead)
-            if (!conv_wide(tol, PP, QQ) && fills(T, 16)) { lpc = 16; algo = LDSR_ALGO_QUAD; }
-            else if (fills(T, 32)) lpc = 32;
-            else algo = em_scan_supported(T, PP, QQ) ? LDSR_ALGO_SCAN : LDSR_ALGO_SERIAL;
-        }
-    }
-    if (algo != LDSR_ALGO_SERIAL && algo != LDSR_ALGO_SCAN && algo != LDSR_ALGO_PAIR && algo != LDSR_ALGO_QUAD)
-        return fail(LDSR_EINVAL, "unknown algo");
-    if (algo == LDSR_ALGO_SCAN && !em_scan_supported(T, PP, QQ))
-        return fail(LDSR_EINVAL, "LDSR_ALGO_SCAN needs T <= 8192 and p, q <= 8 (and T >= L (L - 1) for its chunk length)");
-    if (algo == LDSR_ALGO_PAIR && !em_pair_supported(Te, PP, QQ, 32, lead > 0))
-        return fail(LDSR_EINVAL, "LDSR_ALGO_PAIR needs 65 <= T <= 1024, p, q <= 4 and a series image that leaves room for eight waves per CU (ldsr_em_plan tells)");
-    if (algo == LDSR_ALGO_QUAD && !em_pair_supported(Te, PP, QQ, 16, lead > 0))
-        return fail(LDSR_EINVAL, "LDSR_ALGO_QUAD needs 65 <= T <= 512, p, q <= 4 (ldsr_em_plan tells)");
-    const bool cpw = algo == LDSR_ALGO_PAIR || algo == LDSR_ALGO_QUAD;                // the pair family's body
-    if (algo_used) *algo_used = algo;
-    const int cpb = cells_per_block(algo, cpw ? Te : T, PP, QQ, lpc, cpw ? lead : 0);
-    WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_cells, algo_layout,
-                           cells_per_block(algo_layout, T, PP, QQ));
-    // (the scan kernel's image serves the winners' FIT pass of the restart-grid entries; the bare device
-    // entries run no smoother behind a pair-family launch: series_prep skips it -- 4096 values at config 2)
-    L.build_scan_img = fit_follows || !cpw;
-    if (cpw) {       // the image of the member that runs (the room is for the largest)
-        long sz = 0;
-        em_pair_layout(Te, PP, QQ, lpc, &L.img2_L, &sz, lead > 0);
-        L.img2_NL = lpc;
-        L.lead = lead;
-    } else {
-        L.img2_stride = 0;       // no pair-family launch: series_prep skips its images
-        L.img3_stride = 0;
-    }
-    if (workspace_bytes < L.total)
+    EmPlanIn in;
+    in.T = T; in.p = p; in.q = q; in.niter = E.niter; in.tol = E.tol; in.algo = E.algo;
+    in.lead_steps = E.lead_steps; in.lead_force = E.lead_force; in.cus = device_cu_count(E.device);
+    in.off = E.plan_off ? E.plan_off : cell_offsets;
+    in.n_series = E.plan_off ? E.plan_ns : n_series;
+    const EmPlan pl = E.plan = em_plan(in);
+    if (!pl.ok) return fail(pl.err, pl.msg);
+    const int PP = pl.PP, QQ = pl.QQ, cpb = pl.cpb;
+    const WsLayout &L = E.layout = ws_layout(n_series, T, PP, QQ, E.shared_uv, n_cells, pl.algo_layout, pl.layout_cpb);
+    if (E.workspace_bytes < L.total)
         return fail(LDSR_EINVAL, "workspace too small: need " + std::to_string(L.total) + " bytes");
-    if (((size_t)d_workspace & 255) != 0) return fail(LDSR_EINVAL, "workspace must be 256-byte aligned");
-    HIPCHK(hipSetDevice(device));
-    char *ws = (char *)d_workspace;
+    if (((size_t)E.workspace & 255) != 0) return fail(LDSR_EINVAL, "workspace must be 256-byte aligned");
+    HIPCHK(hipSetDevice(E.device));
+    char *ws = (char *)E.workspace;
 
-    // block table: blocks never straddle a series.  Static mapping (serial kernel; scan kernel
-    // when tol == 0, i.e. every cell runs exactly niter iterations): (series, first cell, n cells
-    // of the block).  Work queue (scan kernel, tol > 0): (series, first cell of the SERIES, n
-    // cells of the series) -- waves pull cells from the per-series queue, so a wave whose cell
-    // converges early takes the next one instead of idling.
-    const bool use_queue = (algo == LDSR_ALGO_SCAN && scan_uses_queue(T, PP, QQ, tol)) ||
-                           (cpw && (tol > 0.0 || (lead > 0 && (PP > 4 || QQ > 4))));   // (wide LEAD forms: work-queue schedule only)
-    std::vector<int> bs, bc, bn;
+    // block table: blocks never straddle a series.  Static schedule: (series, first cell, n cells of
+    // the block).  Work queue: (series, first cell of the SERIES, n cells of the series) -- waves pull
+    // cells from the per-series queue.
+    std::vector<int> tab, bc, bn;     // (tab: the series column, then the other two)
     for (int s = 0; s < n_series; s++)
         for (int c = cell_offsets[s]; c < cell_offsets[s + 1]; c += cpb) {
-            bs.push_back(s);
-            if (use_queue) {
-                bc.push_back(cell_offsets[s]);
-                bn.push_back(cell_offsets[s + 1] - cell_offsets[s]);
-            } else {
-                bc.push_back(c);
-                bn.push_back(std::min(cpb, cell_offsets[s + 1] - c));
-            }
+            tab.push_back(s);
+            bc.push_back(pl.queue ? cell_offsets[s] : c);
+            bn.push_back(pl.queue ? cell_offsets[s + 1] - cell_offsets[s] : std::min(cpb, cell_offsets[s + 1] - c));
         }
-    const int n_blocks = (int)bs.size();
+    const int n_blocks = (int)tab.size();
     if (n_blocks > L.max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow");
-    std::vector<int> tab;
-    tab.reserve(3 * (size_t)n_blocks);
-    tab.insert(tab.end(), bs.begin(), bs.end());
     tab.insert(tab.end(), bc.begin(), bc.end());
     tab.insert(tab.end(), bn.begin(), bn.end());
     int *d_tab = (int *)(ws + L.blk);
-    // Steady form of the two-cells-per-wave kernel (fully observed series, chunks of >= 24 steps):
-    // series_prep also orders every series' cells by predicted slowness (em_pair_impl.h
-    // em_pair_body_steady); it reads the cell offsets from the device copy behind the block table.
-    const bool steady_launch = cpw && lpc == 32 && lead == 0 && pair_steady(L.img2_L, 32, PP, QQ) && order_enabled();
-    if (steady_launch) {
-        tab.insert(tab.end(), cell_offsets, cell_offsets + n_series + 1);
-        L.order_on = true;
-        L.order_cpb = use_queue ? 0 : cpb;
-        L.order_ntr = L.img2_L - 1;
-        L.order_theta0 = d_theta0;
-        L.order_off = d_tab + 3 * n_blocks;
+    const bool scan_img = E.fit_follows || !pl.cpw;
+    PrepParams pp = prep_params(n_series, T, p, q, PP, QQ, E.y, E.u, E.v, E.shared_uv, ws, L, scan_img);
+    if (pl.cpw) {       // the image of the member that runs (the room is for the largest)
+        pp.img2 = L.img2_stride ? (double *)(ws + L.img2) : nullptr;
+        pp.img2_stride = L.img2_stride;
+        pp.L2 = pl.chunk;
+        pp.NL2 = pl.lpc;
+        pp.lead = pl.lead;
+        pp.img3 = (pl.lead > 0 && L.img3_stride) ? (double *)(ws + L.img3) : nullptr;
+        pp.img3_stride = L.img3_stride;
     }
-    rc = stage_h2d_async(device, stream, d_tab, tab.data(), sizeof(int) * tab.size());
+    if (pl.steady_order) {     // (series_prep reads the cell offsets from the device copy behind the block table)
+        tab.insert(tab.end(), cell_offsets, cell_offsets + n_series + 1);
+        pp.perm = (int *)(ws + L.perm);
+        pp.perm_key = (int *)(ws + L.perm_key);
+        pp.cell_off = d_tab + 3 * n_blocks;
+        pp.theta0 = E.theta0;
+        pp.order_cpb = pl.queue ? 0 : cpb;
+        pp.order_ntr = pl.chunk - 1;
+    }
+    rc = stage_h2d_async(E.device, E.stream, d_tab, tab.data(), sizeof(int) * tab.size());
     if (rc) return rc;
-    rc = prepare_series(stream, n_series, T, p, q, PP, QQ, d_y, d_u, d_v, shared_uv, ws, L);
-    if (rc) return rc;
+    HIPCHK(launch_series_prep(pp, n_series, E.stream));
 
     EmParams prm;
-    prm.T = T; prm.p = p; prm.q = q; prm.has_u = d_u != nullptr; prm.has_v = d_v != nullptr;
-    prm.niter = niter; prm.n_cells = n_cells; prm.tol = tol;
-    prm.liks_nanfill = liks_nanfill;
-    prm.abort = abort_flag;
+    prm.T = T; prm.p = p; prm.q = q; prm.has_u = E.u != nullptr; prm.has_v = E.v != nullptr;
+    prm.niter = E.niter; prm.n_cells = n_cells; prm.tol = E.tol;
+    prm.liks_nanfill = E.liks_nanfill;
+    prm.abort = E.abort_flag;
     prm.yp = (const double *)(ws + L.yp);
     prm.yz = (const double *)(ws + L.yz);
     prm.up = (const double *)(ws + L.up);
     prm.vp = (const double *)(ws + L.vp);
-    prm.u_stride = shared_uv ? 0 : (long)T * PP;
-    prm.v_stride = shared_uv ? 0 : (long)T * QQ;
-    prm.img = (const double *)(ws + L.img);
+    prm.u_stride = E.shared_uv ? 0 : (long)T * PP;
+    prm.v_stride = E.shared_uv ? 0 : (long)T * QQ;
+    prm.img = scan_img ? (const double *)(ws + L.img) : nullptr;
     prm.img_stride = L.img_stride;
-    prm.img2 = L.img2_stride ? (const double *)(ws + L.img2) : nullptr;
-    prm.img2_stride = L.img2_stride;
-    prm.lead = cpw ? lead : 0;
-    prm.img3 = (cpw && lead > 0) ? (const double *)(ws + L.img3) : nullptr;
-    prm.img3_stride = L.img3_stride;
+    prm.img2 = pp.img2;
+    prm.img2_stride = pp.img2_stride;
+    prm.lead = pl.lead;
+    prm.img3 = pp.img3;
+    prm.img3_stride = pp.img3_stride;
     prm.fitX = prm.fitY = prm.fitV = prm.fitJ = prm.pen = nullptr;
     prm.lambda = 0.0;
     prm.stdlik = 1;
@@ -919,29 +666,25 @@ static int em_batch_device_impl(int device, hipStream_t stream, int n_series, in
     prm.blk_series = d_tab;
     prm.blk_cell0 = d_tab + n_blocks;
     prm.blk_ncell = d_tab + 2 * n_blocks;
-    prm.theta0 = d_theta0;
-    prm.theta = d_theta; prm.lik = d_lik; prm.liks = d_liks;
-    prm.n_iter = d_n_iter; prm.status = d_status;
+    prm.theta0 = E.theta0;
+    prm.theta = E.theta; prm.lik = E.lik; prm.liks = E.liks;
+    prm.n_iter = E.n_iter; prm.status = E.status;
     prm.queue = (int *)(ws + L.queue);
-    prm.perm = steady_launch ? (const int *)(ws + L.perm) : nullptr;
+    prm.perm = pl.steady_order ? (const int *)(ws + L.perm) : nullptr;
     prm.scratch = (double *)(ws + L.scratch);
     prm.scratch_stride = L.scratch_stride;
     int slot;
-    HIPCHK(prof_begin(device, stream, &slot));
-    {
-        char nm[160];
-        if (cpw) em_pair_kernel_name(Te, PP, QQ, lpc, use_queue, nm, sizeof(nm), lead > 0);
-        else if (algo == LDSR_ALGO_SCAN) em_scan_kernel_name(T, PP, QQ, use_queue, false, nm, sizeof(nm));
-        else em_serial_kernel_name(T, PP, QQ, nm, sizeof(nm));
-        remember_kernel(device, nm);
-    }
-    if (cpw)
-        HIPCHK(launch_em_pair(prm, PP, QQ, lpc, n_blocks, use_queue, stream));
-    else if (algo == LDSR_ALGO_SCAN)
-        HIPCHK(launch_em_scan(prm, PP, QQ, n_blocks, use_queue, false, stream));
+    HIPCHK(prof_begin(E.device, E.stream, &slot));
+    char nm[160];
+    em_plan_kernel_name(pl, nm, sizeof(nm));
+    remember_kernel(E.device, nm);
+    if (pl.cpw)
+        HIPCHK(launch_em_pair(prm, PP, QQ, pl.lpc, n_blocks, pl.queue, E.stream));
+    else if (pl.algo == LDSR_ALGO_SCAN)
+        HIPCHK(launch_em_scan(prm, PP, QQ, n_blocks, pl.queue, false, E.stream));
     else
-        HIPCHK(launch_em_serial(prm, PP, QQ, n_blocks, stream));
-    HIPCHK(prof_end(stream, slot));
+        HIPCHK(launch_em_serial(prm, PP, QQ, n_blocks, E.stream));
+    HIPCHK(prof_end(E.stream, slot));
     return LDSR_OK;
 }
 
@@ -952,11 +695,16 @@ extern "C" int ldsr_em_batch_device_lead(int device, void *stream_, int n_series
                                          double *d_theta, double *d_lik, int *d_n_iter, int *d_status,
                                          double *d_liks, void *d_workspace, size_t workspace_bytes,
                                          int lead_steps) {
-    return em_batch_device_impl(device, (hipStream_t)stream_, n_series, T, p, q, d_y, d_u, d_v,
-                                shared_uv, cell_offsets, d_theta0, niter, tol, algo, d_theta, d_lik,
-                                d_n_iter, d_status, d_liks, 1, d_workspace, workspace_bytes, nullptr,
-                                lead_steps < 0 ? 1 : -1, nullptr, lead_steps < 0 ? 0 : lead_steps, nullptr, 0,
-                                nullptr, 0, false);
+    EmLaunch E;
+    E.device = device; E.stream = (hipStream_t)stream_;
+    E.n_series = n_series; E.T = T; E.p = p; E.q = q; E.shared_uv = shared_uv;
+    E.y = d_y; E.u = d_u; E.v = d_v; E.cell_offsets = cell_offsets; E.theta0 = d_theta0;
+    E.niter = niter; E.tol = tol; E.algo = algo;
+    E.theta = d_theta; E.lik = d_lik; E.n_iter = d_n_iter; E.status = d_status; E.liks = d_liks;
+    E.workspace = d_workspace; E.workspace_bytes = workspace_bytes;
+    E.lead_steps = lead_steps < 0 ? -1 : lead_steps;
+    E.fit_follows = false;
+    return em_batch_device_impl(E);
 }
 
 extern "C" int ldsr_em_batch_device(int device, void *stream_, int n_series, int T, int p, int q,
@@ -965,10 +713,9 @@ extern "C" int ldsr_em_batch_device(int device, void *stream_, int n_series, int
                                     const double *d_theta0, int niter, double tol, int algo,
                                     double *d_theta, double *d_lik, int *d_n_iter, int *d_status,
                                     double *d_liks, void *d_workspace, size_t workspace_bytes) {
-    return em_batch_device_impl(device, (hipStream_t)stream_, n_series, T, p, q, d_y, d_u, d_v,
-                                shared_uv, cell_offsets, d_theta0, niter, tol, algo, d_theta, d_lik,
-                                d_n_iter, d_status, d_liks, 1, d_workspace, workspace_bytes, nullptr, -1,
-                                nullptr, -1, nullptr, 0, nullptr, 0, false);
+    return ldsr_em_batch_device_lead(device, stream_, n_series, T, p, q, d_y, d_u, d_v, shared_uv,
+                                     cell_offsets, d_theta0, niter, tol, algo, d_theta, d_lik, d_n_iter,
+                                     d_status, d_liks, d_workspace, workspace_bytes, 0);
 }
 
 // One Kalman_smoother pass (src/EM.cpp:22-131) for n cells on prepared series: the FIT form of
@@ -987,19 +734,17 @@ static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, 
         const int *d_tab = d_tab_prebuilt;      // [3][n]: one block per cell, filled on the device
         int n_blocks = n;
         if (!d_tab) {
-            std::vector<int> bs, bc, bn;
+            std::vector<int> tab, bc, bn;           // (tab: the series column, then the other two)
             for (int c = 0; c < n;) {               // blocks never straddle a series
                 int e = c + 1;
                 while (e < n && e - c < cpb && series_of_cell[(size_t)e] == series_of_cell[(size_t)c]) e++;
-                bs.push_back(series_of_cell[(size_t)c]);
+                tab.push_back(series_of_cell[(size_t)c]);
                 bc.push_back(c);
                 bn.push_back(e - c);
                 c = e;
             }
-            n_blocks = (int)bs.size();
+            n_blocks = (int)tab.size();
             if (n_blocks > L.max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow (fit)");
-            std::vector<int> tab;
-            tab.insert(tab.end(), bs.begin(), bs.end());
             tab.insert(tab.end(), bc.begin(), bc.end());
             tab.insert(tab.end(), bn.begin(), bn.end());
             int *d_ws_tab = (int *)(ws + L.blk);
@@ -1067,10 +812,8 @@ static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, 
 struct Slice {
     // inputs (host pointers already offset to the slice; `off` are local cell offsets)
     int device = 0, n_series = 0, T = 0, p = 0, q = 0, shared_uv = 0, niter = 0, algo = 0;
-    int dense_hint = -1;     // 1: every y_t of every series is finite (AUTO's kernel choice with tol > 0)
-    int algo_used = 0;       // the algorithm the batch launch resolved to
-    int lead_used = 0;       // ... and the closed-form lead it used
-    int lead_hint = -1;      // steps before the first observation of any series
+    int lead_steps = 0;      // data facts found in y (EmPlanIn): -1 fully observed, else the all-missing lead
+    EmPlan plan;             // what the batch launch ran
     double tol = 0.0;
     const double *y = nullptr, *u = nullptr, *v = nullptr, *theta0 = nullptr;
     std::vector<int> off;
@@ -1078,9 +821,7 @@ struct Slice {
     // cells [g_lo[s], g_lo[s] + off[s+1] - off[s]) of the caller's arrays -- theta0 / theta / lik /
     // n_iter / status / liks are the caller's whole arrays, gathered and scattered per series.
     std::vector<int> g_lo;
-    // AUTO looks at the whole call, not at the slice: the kernel (hence the rounding of the results)
-    // must not depend on how many devices share the work
-    const int *plan_off = nullptr;
+    const int *plan_off = nullptr;      // the whole call's offsets (EmLaunch), several devices only
     int plan_ns = 0;
     // host outputs of phase 1 (liks optional: the full [n_cells][niter] trace, NaN padded)
     double *theta = nullptr, *lik = nullptr, *liks = nullptr;
@@ -1154,6 +895,23 @@ static void slice_scatter(const Slice &S, const char *pout) {
     }
 }
 
+// the EM launch of a slice on its arena: the prepared inputs, the per-cell outputs and the workspace
+static EmLaunch slice_launch(const Slice &S) {
+    const Arena *A = S.lease.a;
+    EmLaunch E;
+    E.device = S.device; E.stream = A->stream;
+    E.n_series = S.n_series; E.T = S.T; E.p = S.p; E.q = S.q; E.shared_uv = S.shared_uv;
+    E.y = (const double *)(A->dev + S.d_y);
+    E.u = S.u ? (const double *)(A->dev + S.d_u) : nullptr;
+    E.v = S.v ? (const double *)(A->dev + S.d_v) : nullptr;
+    E.niter = S.niter; E.tol = S.tol;
+    E.theta = (double *)(A->dev + S.d_theta); E.lik = (double *)(A->dev + S.d_lik);
+    E.n_iter = (int *)(A->dev + S.d_nit); E.status = (int *)(A->dev + S.d_st);
+    E.workspace = A->dev + S.d_ws; E.workspace_bytes = S.wsb;
+    E.lead_steps = S.lead_steps;
+    return E;
+}
+
 static int slice_run(Slice &S) {
     S.n_cells = S.off[S.n_series];
     S.P = 6 + S.p + S.q;
@@ -1185,10 +943,6 @@ static int slice_run(Slice &S) {
     S.d_liks = c.take(S.trace_on_device ? trace_bytes : 0);
     S.wsb = ldsr_em_workspace_bytes(S.n_series, T, S.p, S.q, n, S.algo);
     if (!S.wsb) return fail(LDSR_EINVAL, "unsupported (T, p, q, algo) combination");
-    {   // the layout em_batch_device_impl will carve out of the workspace (phase 2 reuses it)
-        const int a = resolve_algo(S.algo, T, S.PP, S.QQ);
-        S.L = ws_layout(S.n_series, T, S.PP, S.QQ, S.shared_uv, n, a, cells_per_block(a, T, S.PP, S.QQ));
-    }
     S.d_ws = c.take(S.wsb);
     const WinLayout W = win_layout(std::max(S.max_winners, 1), P, T, S.niter);
     S.d_w = c.take(S.max_winners > 0 ? W.total : 0);
@@ -1209,7 +963,6 @@ static int slice_run(Slice &S) {
         bool all_obs = true;
         const size_t ny = (size_t)S.n_series * T;
         for (size_t i = 0; i < ny && all_obs; i++) all_obs = std::isfinite(S.y[i]);
-        S.dense_hint = all_obs ? 1 : 0;
         // all-missing lead common to every series (the pair family's closed form)
         int lead = T;
         for (int s = 0; s < S.n_series && lead > 0; s++) {
@@ -1217,7 +970,7 @@ static int slice_run(Slice &S) {
             while (t < lead && !std::isfinite(S.y[(size_t)s * T + t])) t++;
             lead = std::min(lead, t);
         }
-        S.lead_hint = lead;
+        S.lead_steps = all_obs ? -1 : lead;
     }
     if (S.u) memcpy(pin + (S.d_u - S.d_in), S.u, sizeof(double) * nuv * T * S.p);
     if (S.v) memcpy(pin + (S.d_v - S.d_in), S.v, sizeof(double) * nuv * T * S.q);
@@ -1228,15 +981,18 @@ static int slice_run(Slice &S) {
     memcpy(pin + (S.d_off - S.d_in), S.off.data(), sizeof(int) * ((size_t)S.n_series + 1));
     HIPCHK(hipMemcpyAsync(A->dev + S.d_in, pin, S.in_bytes, hipMemcpyHostToDevice, A->stream));
 
-    rc = em_batch_device_impl(
-        S.device, A->stream, S.n_series, T, S.p, S.q, (const double *)(A->dev + S.d_y),
-        S.u ? (const double *)(A->dev + S.d_u) : nullptr, S.v ? (const double *)(A->dev + S.d_v) : nullptr,
-        S.shared_uv, S.off.data(), (const double *)(A->dev + S.d_th0), S.niter, S.tol, S.algo,
-        (double *)(A->dev + S.d_theta), (double *)(A->dev + S.d_lik), (int *)(A->dev + S.d_nit),
-        (int *)(A->dev + S.d_st), S.trace_on_device ? (double *)(A->dev + S.d_liks) : nullptr,
-        S.liks != nullptr, A->dev + S.d_ws, S.wsb, intr_flag_for_kernels(), S.dense_hint, &S.algo_used,
-        S.lead_hint, &S.lead_used, 0, S.plan_off, S.plan_ns);
+    EmLaunch E = slice_launch(S);
+    E.cell_offsets = S.off.data();
+    E.theta0 = (const double *)(A->dev + S.d_th0);
+    E.algo = S.algo;
+    E.liks = S.trace_on_device ? (double *)(A->dev + S.d_liks) : nullptr;
+    E.liks_nanfill = S.liks != nullptr;
+    E.abort_flag = intr_flag_for_kernels();
+    E.plan_off = S.plan_off; E.plan_ns = S.plan_ns;
+    rc = em_batch_device_impl(E);
     if (rc) return rc;
+    S.plan = E.plan;
+    S.L = E.layout;         // (phase 2 reuses the prepared series and the scan kernel's image)
     char *pout = A->pin + S.p_out;
     if (S.fuse && S.trace_on_device) {
         // selection, winner extraction and the winners' fit behind the EM kernel, one sync
@@ -1346,21 +1102,18 @@ static int slice_fit_winners(Slice &S, int n_w, const int *w_series, const int *
     if (!S.trace_on_device && liks_w) {
         // the per-cell traces were too large to keep: re-run the winners alone (one cell per
         // series; a cell's result does not depend on its position in the grid) with a trace
-        std::vector<int> sel_off((size_t)S.n_series + 1, 0), order((size_t)n_w);
+        std::vector<int> sel_off((size_t)S.n_series + 1, 0);
         for (int i = 0; i < n_w; i++) sel_off[(size_t)w_series[i] + 1] = 1;
         for (int s = 0; s < S.n_series; s++) sel_off[(size_t)s + 1] += sel_off[(size_t)s];
         for (int i = 1; i < n_w; i++)
             if (w_series[i] <= w_series[i - 1]) return fail(LDSR_EINVAL, "internal: winners must be sorted by series");
-        const size_t nuv = S.shared_uv ? 1 : (size_t)S.n_series;
-        (void)nuv;
-        int rc = em_batch_device_impl(
-            S.device, A->stream, S.n_series, T, S.p, S.q, (const double *)(A->dev + S.d_y),
-            S.u ? (const double *)(A->dev + S.d_u) : nullptr, S.v ? (const double *)(A->dev + S.d_v) : nullptr,
-            S.shared_uv, sel_off.data(), (const double *)(dw + W.theta0), niter, S.tol,
-            S.algo_used ? S.algo_used : S.algo,       // the kernel of the batch run, whatever AUTO would pick for a few cells
-            (double *)(A->dev + S.d_theta), (double *)(A->dev + S.d_lik), (int *)(A->dev + S.d_nit),
-            (int *)(A->dev + S.d_st), (double *)(dw + W.liks), 1, ws, S.wsb, nullptr, S.dense_hint, nullptr, -1,
-            nullptr, S.lead_used);
+        EmLaunch E = slice_launch(S);
+        E.cell_offsets = sel_off.data();
+        E.theta0 = (const double *)(dw + W.theta0);
+        E.algo = S.plan.algo;           // the kernel of the batch run, whatever AUTO would pick for a few cells
+        E.lead_force = S.plan.lead;
+        E.liks = (double *)(dw + W.liks);
+        int rc = em_batch_device_impl(E);
         if (rc) return rc;
     }
     // the winners' fit: one smoother pass at theta_w on the prepared series
@@ -1657,9 +1410,7 @@ static int run_fit_kernel(int mode, int device, int n_series, int T, int p, int 
     rc = arena_acquire(device, &lease.a);
     if (rc) return rc;
     Arena *A = lease.a;
-    WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_cells, LDSR_ALGO_SCAN, 1);
-    L.img2_stride = 0;       // no pair-family launch here: series_prep builds the scan image only
-    L.img3_stride = 0;
+    const WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_cells, LDSR_ALGO_SCAN, 1);
     // the serial smoother uses X / V as its filtered-state strip; the scan FIT kernel needs none
     const bool need_strip = !(mode == 0 || mode == 3) || !em_scan_supported(T, PP, QQ);
     Carver c;
@@ -1691,10 +1442,10 @@ static int run_fit_kernel(int mode, int device, int n_series, int T, int p, int 
         for (int cc = cell_offsets[s]; cc < cell_offsets[s + 1]; cc++) soc[cc] = s;
     HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
     char *ws = dev + o_ws;
-    rc = prepare_series(A->stream, n_series, T, p, q, PP, QQ, (const double *)(dev + o_y),
-                        u ? (const double *)(dev + o_u) : nullptr,
-                        v ? (const double *)(dev + o_v) : nullptr, shared_uv, ws, L);
-    if (rc) return rc;
+    HIPCHK(launch_series_prep(prep_params(n_series, T, p, q, PP, QQ, (const double *)(dev + o_y),
+                                          u ? (const double *)(dev + o_u) : nullptr,
+                                          v ? (const double *)(dev + o_v) : nullptr, shared_uv, ws, L, true),
+                              n_series, A->stream));
 
     std::vector<int> soc_v(soc, soc + n_cells);
     char *pout = pin + in_bytes;

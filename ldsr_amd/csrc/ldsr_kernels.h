@@ -96,6 +96,33 @@ void em_scan_kernel_name(int T, int PP, int QQ, bool queue, bool fit, char *buf,
 void em_serial_kernel_name(int T, int PP, int QQ, char *buf, size_t len);
 #include <string>
 void em_kernel_inventory(std::string &out);      // names of every compiled scan / pair instantiation, one per line
+
+// Which EM kernel a launch runs (em_plan.hip): the one place that decides it, for the launches and
+// for the plan queries of the C ABI.  Host code, no HIP calls.
+struct EmPlanIn {
+    int T = 0, p = 0, q = 0, niter = 0, algo = 0;     // algo: the requested LDSR_ALGO_*
+    double tol = 0.0;
+    int lead_steps = 0;            // data facts: -1 every y_t observed, 0 unknown, > 0 the first lead_steps steps of every series missing
+    int lead_force = 0;            // > 0: the pair family runs with this lead (a re-run of part of a batch)
+    const int *off = nullptr;      // the whole call's cell offsets [n_series + 1] on a device of cus CUs;
+    int n_series = 0, cus = 0;     // off = null: a launch that fills the device
+};
+struct EmPlan {
+    bool ok = false;
+    int err = 0;                   // !ok: LDSR_E* code and message
+    const char *msg = "";
+    int T = 0, PP = 0, QQ = 0;
+    int algo_layout = 0, layout_cpb = 0;    // what the workspace is sized and laid out for (the resolved request)
+    int algo = 0;                  // what runs: LDSR_ALGO_SERIAL, _SCAN, _PAIR or _QUAD
+    bool cpw = false;              // the pair family (PAIR or QUAD) with lpc lanes per cell (32: two cells per wave, 16: four)
+    int lpc = 32, chunk = 0;       // ... and chunk length of its series image
+    int lead = 0, Te = 0;          // closed-form lead, and the steps the sweeps work on (T - lead)
+    bool queue = false;            // per-series work queue (else static schedule)
+    int cpb = 0;                   // cells per workgroup
+    bool steady_order = false;     // series_prep orders the cells for the steady form
+};
+EmPlan em_plan(const EmPlanIn &in);
+void em_plan_kernel_name(const EmPlan &pl, char *buf, size_t len);   // as rocprofv3 prints it
 hipError_t launch_gather_winners(const GatherParams &prm, hipStream_t stream);
 hipError_t launch_select_winners(const SelectParams &prm, hipStream_t stream);
 hipError_t launch_smooth(const SmoothParams &prm, int PP, int QQ, hipStream_t stream);

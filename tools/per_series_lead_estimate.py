@@ -3,7 +3,7 @@
 
 The LEAD kernels sweep the tail [T - tail, T) of every series of a call with ONE kernel instantiation,
 i.e. one chunk length L = ceil(tail / lanes per cell); the call's tail is max(T - shortest lead, 80)
-rounded up to a multiple of 16 (ldsr_api.hip lead_tail).  A lane's sweep costs L steps whatever the
+rounded up to a multiple of 16 (em_plan.hip lead_tail).  A lane's sweep costs L steps whatever the
 number of active lanes, so a per-series lead inside one launch moves steps from the sweeps to the lead
 of THAT series but does not shorten any lane's chunk: it saves nothing.  What can save is grouping the
 series by tail class into launches of their own chunk length.  This script counts both."""
