@@ -25,6 +25,10 @@
  *   ldsr_propagate_batch     _ldsr_propagate (src/RcppExports.cpp:56-69 -> src/EM.cpp:295-356)
  *   ldsr_penalized_lik_batch penalized_likelihood of R/LDS_GA.R:28-44 for a whole GA population
  *   ldsr_select_restart      the argmax-with-C>0 rule of R/LDS_reconstruction.R:50-58
+ *   ldsr_simulate_batch      LDS_rep / one_LDS_rep (R/stochastics.R:18-63): num_reps stochastic
+ *                            replicates of each of n_models thetas in one launch; with the uniforms
+ *                            R would draw (ldsr_simulate_draw_count) the result is set.seed(k);
+ *                            LDS_rep(...) draw for draw
  *
  * Data conventions (identical to the bytes R hands to .Call):
  *   y      [n_series][T]        double, NaN / NA_real_ = missing
@@ -234,6 +238,39 @@ int ldsr_penalized_lik_batch(int device, int n_series, int T, int p, int q, cons
                              const double *u, const double *v, int shared_uv,
                              const int *cell_offsets, const double *theta, double lambda,
                              double *pl);
+
+/* Stochastic replicates: one_LDS_rep / LDS_rep (R/stochastics.R:18-63) for n_models thetas x
+ * num_reps replicates of T steps,
+ *   x_1 ~ N(0, V1), x_{t+1} = A x_t + B u_t + q_t, y_t = C x_t + D v_t + r_t, q_t ~ N(0, Q), r_t ~ N(0, R),
+ *   simQ_t = exp(y_t + mu) if exp_trans, else y_t + mu   (x_1 has mean 0: mu1 is not used).
+ *   theta  [n_models][6+p+q]; u [n_models][T][p] / v [n_models][T][q] (shared_uv: one [T][p] / [T][q]
+ *          for all models), either NULL = that term dropped (no upper limit on p, q); mu [n_models]
+ *          or NULL (= 0).
+ *   uniforms  NULL: counter mode -- uniform i of replicate r of model m is SplitMix64 of (seed,
+ *          m * 2^32 + first_rep + r, i), so replicates do not depend on how they are split over calls;
+ *          otherwise R-stream mode: R's unif_rand() values in the order LDS_rep consumes them (models
+ *          one after the other, each model's replicates one after the other; first_rep is unused).
+ *          Normals are R's "Inversion" rule: two uniforms each, none for a zero, NaN, negative or
+ *          infinite variance (R's rnorm returns 0 / NaN there without drawing).
+ *   simX, simY, simQ  [n_models][num_reps][T], each may be NULL (not computed).
+ * Host pointers; copies in, runs on `device`, copies out. */
+int ldsr_simulate_batch(int device, int n_models, int T, int p, int q, const double *u,
+                        const double *v, int shared_uv, const double *theta, const double *mu,
+                        int num_reps, int first_rep, int exp_trans, unsigned long long seed,
+                        const double *uniforms, double *simX, double *simY, double *simQ);
+/* Uniforms one such call consumes in R-stream mode (host code); offsets [n_models + 1] (may be NULL)
+ * receives where each model's uniforms start.  A negative value (-LDSR_EINVAL) for bad arguments. */
+long long ldsr_simulate_draw_count(int n_models, int T, int p, int q, const double *theta,
+                                   int num_reps, long long *offsets);
+/* Same as ldsr_simulate_batch with DEVICE pointers, asynchronous on `stream` (NULL = default
+ * stream).  R-stream mode also takes d_offsets: the first n_models offsets of
+ * ldsr_simulate_draw_count, copied to the device (NULL in counter mode). */
+int ldsr_simulate_batch_device(int device, void *stream, int n_models, int T, int p, int q,
+                               const double *d_u, const double *d_v, int shared_uv,
+                               const double *d_theta, const double *d_mu, int num_reps,
+                               int first_rep, int exp_trans, unsigned long long seed,
+                               const double *d_uniforms, const long long *d_offsets,
+                               double *d_simX, double *d_simY, double *d_simQ);
 
 /* User interrupts during a run (the reference calls Rcpp::checkUserInterrupt() every 100 EM
  * iterations, src/EM.cpp:261-262).  While a callback is registered, the thread that called an

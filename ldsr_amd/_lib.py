@@ -52,6 +52,13 @@ SIGNATURES = {
                                        C.c_int, _ip, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "ldsr_penalized_lik_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.c_int, _ip, _dp, C.c_double, _dp]),
+    "ldsr_simulate_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp,
+                                      _dp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, _dp, _dp, _dp]),
+    "ldsr_simulate_draw_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int,
+                                                C.POINTER(C.c_longlong)]),
+    "ldsr_simulate_batch_device": (C.c_int, [C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                             C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
+                                             _vp, _vp, _vp, _vp, _vp]),
     "ldsr_profile_enable": (None, [C.c_int]),
     "ldsr_profile_collect": (C.c_int, [_dp, _ip]),
     "ldsr_select_restart": (C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int]),

@@ -127,3 +127,34 @@ hipError_t launch_gather_winners(const GatherParams &prm, hipStream_t stream);
 hipError_t launch_select_winners(const SelectParams &prm, hipStream_t stream);
 hipError_t launch_smooth(const SmoothParams &prm, int PP, int QQ, hipStream_t stream);
 hipError_t launch_mstep(const SmoothParams &prm, int PP, int QQ, hipStream_t stream);
+
+// Stochastic replicates (simulate.hip): one_LDS_rep / LDS_rep, R/stochastics.R:18-63.
+// R's rnorm(n, 0, sd) with sd = sqrt(var) (nmath rnorm): a NaN, negative or infinite sd gives NaN and
+// a zero sd gives 0, both without consuming a uniform; otherwise one norm_rand() = two unif_rand().
+// Returns 1 if R draws, else 0 with the returned value in *fixed.
+__host__ __device__ inline int sim_draws(double var, double *fixed) {
+    const double sd = sqrt(var);
+    if (!(sd >= 0.0) || sd == INFINITY) { *fixed = NAN; return 0; }
+    if (sd == 0.0) { *fixed = 0.0; return 0; }
+    *fixed = 0.0;
+    return 1;
+}
+// uniforms one replicate consumes: [x_1 from V1] [q_1..q_T from Q] [r_1..r_T from R], two per draw
+__host__ __device__ inline long long sim_draws_per_rep(const double *theta, int p, int q, int T) {
+    double f;
+    const int P = 6 + p + q;
+    return 2 * ((long long)sim_draws(theta[P - 1], &f) + (long long)T * sim_draws(theta[2 + p + q], &f) +
+                (long long)T * sim_draws(theta[3 + p + q], &f));
+}
+struct SimParams {
+    int n_models, T, p, q, num_reps, first_rep, exp_trans;
+    const double *u, *v;           // [.][T][p] / [.][T][q] time-major, or null (term dropped)
+    long long u_stride, v_stride;  // doubles from one model's inputs to the next (0: one shared series)
+    const double *theta;           // [n_models][6 + p + q]
+    const double *mu;              // [n_models] or null (0)
+    unsigned long long seed;       // counter mode
+    const double *uniforms;        // R-stream mode (null: counter mode) ...
+    const long long *draw_off;     // ... and [n_models] index of each model's first uniform there
+    double *simX, *simY, *simQ;    // [n_models][num_reps][T], each may be null
+};
+hipError_t launch_simulate(const SimParams &prm, hipStream_t stream);
