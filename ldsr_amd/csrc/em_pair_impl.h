@@ -87,9 +87,19 @@ __host__ __device__ constexpr bool pair_steady(int L, int LPC, int PP, int QQ) {
 // Does the (L, LPC, PP, QQ) member leave room for a CU's waves: the series image and eight strips (wide
 // inputs -- padded p or q = 8, LEAD forms only: four) within 160 KiB.  ONE rule for the plan
 // (kernels_scan.hip pair_plan) and for what is compiled (em_pair_launch.inc).
+// Wide inputs: padded p or q = 8.
+__host__ __device__ constexpr bool pair_wide(int PP, int QQ) { return PP > 4 || QQ > 4; }
 __host__ __device__ constexpr bool pair_member_fits(int L, int LPC, int PP, int QQ) {
-    const bool wide = PP > 4 || QQ > 4;
-    return (pair_image_doubles(L, PP, QQ, LPC) + (wide ? 4 : 8) * pair_strip_doubles(L)) * 8 <= 160 * 1024;
+    return (pair_image_doubles(L, PP, QQ, LPC) + (pair_wide(PP, QQ) ? 4 : 8) * pair_strip_doubles(L)) * 8 <= 160 * 1024;
+}
+// Which instantiations of a member exist, for the launcher (em_pair_launch.inc), the inventory and the plans
+// (kernels_scan.hip, em_plan.hip) alike.  LEAD forms (closed form for an all-missing lead, the sweeps work on the
+// tail): chunks of <= 16 steps.  Wide inputs: the LEAD form with the work-queue schedule, nothing else (the
+// generic sweeps of long chunks do not fit the registers of two waves per SIMD at q = 8).
+constexpr int kPairLeadMaxL = 16;
+__host__ __device__ constexpr bool pair_variant(int PP, int QQ, int L, int LPC, bool queue, bool lead) {
+    if (!pair_member_fits(L, LPC, PP, QQ) || (lead && L > kPairLeadMaxL)) return false;
+    return pair_wide(PP, QQ) ? lead && queue : true;
 }
 
 __device__ __forceinline__ double shfl_d(double x, int src_lane) { return __shfl(x, src_lane, 64); }

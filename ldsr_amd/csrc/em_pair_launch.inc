@@ -1,22 +1,18 @@
-// em_pair_launch.inc -- included by em_pair_L*.hip / em_quad_L*.hip with PAIR_L (and PAIR_LPC = 16
-// for four cells per wave) defined: instantiates the two- / four-cells-per-wave kernel (em_pair_impl.h) for the narrow padded shapes at that chunk length,
-// static and work-queue schedule, and defines its launcher.
+// em_pair_launch.inc -- the translation unit of one pair member (em_members.h), compiled with -DPAIR_L=<L>
+// -DPAIR_LPC=<32: two cells per wave | 16: four>: instantiates the kernel of em_pair_impl.h for every padded
+// (PP, QQ) at that chunk length in the variants pair_variant() names and defines the member's launcher (which
+// exists for every member, even where no (PP, QQ) has a variant: it then returns hipErrorInvalidValue).
 #include "em_pair_impl.h"
 #include "ldsr_kernels.h"
 
-#ifndef PAIR_LPC
-#define PAIR_LPC 32
-#endif
-
-template <int PP, int QQ, bool QUEUE, bool LEAD = false>
+template <int PP, int QQ, bool QUEUE, bool LEAD>
 static hipError_t pair_launch_v(const EmParams &prm, int n_blocks, int wpb, hipStream_t stream) {
     constexpr int L = PAIR_L;
-    const size_t lds = ((size_t)pair_image_doubles(L, PP, QQ, PAIR_LPC) + (size_t)wpb * pair_strip_doubles(L) +
-                        (LEAD ? (size_t)pair_lead_doubles(prm.lead, PAIR_LPC, PP) : 0) +
-                        (!LEAD && pair_steady(L, PAIR_LPC, PP, QQ) ? (size_t)pair_tri_doubles(PP, QQ, PAIR_LPC) : 0)) * sizeof(double);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    // (compiled only where pair_plan can select it: the member's image and strips fit a CU's LDS)
-    if constexpr (pair_member_fits(L, PAIR_LPC, PP, QQ)) {
+    if constexpr (pair_variant(PP, QQ, L, PAIR_LPC, QUEUE, LEAD)) {
+        const size_t lds = ((size_t)pair_image_doubles(L, PP, QQ, PAIR_LPC) + (size_t)wpb * pair_strip_doubles(L) +
+                            (LEAD ? (size_t)pair_lead_doubles(prm.lead, PAIR_LPC, PP) : 0) +
+                            (!LEAD && pair_steady(L, PAIR_LPC, PP, QQ) ? (size_t)pair_tri_doubles(PP, QQ, PAIR_LPC) : 0)) * sizeof(double);
+        if (lds > 160 * 1024) return hipErrorInvalidValue;
         auto kern = em_pair_kernel<PP, QQ, L, PAIR_LPC, QUEUE, LEAD>;
         if (lds > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void *)kern,
@@ -32,34 +28,19 @@ static hipError_t pair_launch_v(const EmParams &prm, int n_blocks, int wpb, hipS
 template <>
 hipError_t launch_em_pair_L<PAIR_L, PAIR_LPC>(const EmParams &prm, int PPv, int QQv, int n_blocks, int wpb,
                                     bool queue, hipStream_t stream) {
-    if (prm.lead > 0 && PAIR_L > 16) return hipErrorInvalidValue;   // (no LEAD form compiled)
-    if ((PPv > 4 || QQv > 4) && (prm.lead <= 0 || !queue)) return hipErrorInvalidValue;   // (wide: LEAD form, work queue)
+    const bool lead = prm.lead > 0;     // LEAD form: closed form for an all-missing lead
     switch (PPv * 16 + QQv) {
-#define CASE_PQ(a, b)                                                                    \
-    case a * 16 + b:                                                                     \
-        return queue ? pair_launch_v<a, b, true>(prm, n_blocks, wpb, stream)             \
-                     : pair_launch_v<a, b, false>(prm, n_blocks, wpb, stream);
-// LEAD forms (closed form for an all-missing lead): short tails only (PAIR_L <= 16)
-#define CASE_PQL(a, b)                                                                   \
-    case a * 16 + b:                                                                     \
-        if constexpr (PAIR_L <= 16) {                                                    \
-            if (prm.lead > 0)                                                            \
-                return queue ? pair_launch_v<a, b, true, true>(prm, n_blocks, wpb, stream)   \
-                             : pair_launch_v<a, b, false, true>(prm, n_blocks, wpb, stream); \
-        }                                                                                \
-        return queue ? pair_launch_v<a, b, true>(prm, n_blocks, wpb, stream)             \
-                     : pair_launch_v<a, b, false>(prm, n_blocks, wpb, stream);
-        CASE_PQL(1, 1) CASE_PQL(1, 2) CASE_PQL(1, 4)
-        CASE_PQL(2, 1) CASE_PQL(2, 2) CASE_PQL(2, 4)
-        CASE_PQL(4, 1) CASE_PQL(4, 2) CASE_PQL(4, 4)
-// wide inputs (padded p or q = 8): the LEAD form with the work-queue schedule, nothing else
-#if PAIR_L <= 16
-#define CASE_WL(a, b) case a * 16 + b: return pair_launch_v<a, b, true, true>(prm, n_blocks, wpb, stream);
-        CASE_WL(1, 8) CASE_WL(2, 8) CASE_WL(4, 8) CASE_WL(8, 1) CASE_WL(8, 2) CASE_WL(8, 4) CASE_WL(8, 8)
-#undef CASE_WL
-#endif
+#define CASE_PQ(a, b)                                                                                  \
+    case a * 16 + b:                                                                                   \
+        return lead ? (queue ? pair_launch_v<a, b, true, true>(prm, n_blocks, wpb, stream)             \
+                             : pair_launch_v<a, b, false, true>(prm, n_blocks, wpb, stream))           \
+                    : (queue ? pair_launch_v<a, b, true, false>(prm, n_blocks, wpb, stream)            \
+                             : pair_launch_v<a, b, false, false>(prm, n_blocks, wpb, stream));
+        CASE_PQ(1, 1) CASE_PQ(1, 2) CASE_PQ(1, 4) CASE_PQ(1, 8)
+        CASE_PQ(2, 1) CASE_PQ(2, 2) CASE_PQ(2, 4) CASE_PQ(2, 8)
+        CASE_PQ(4, 1) CASE_PQ(4, 2) CASE_PQ(4, 4) CASE_PQ(4, 8)
+        CASE_PQ(8, 1) CASE_PQ(8, 2) CASE_PQ(8, 4) CASE_PQ(8, 8)
 #undef CASE_PQ
-#undef CASE_PQL
         default: return hipErrorInvalidValue;
     }
 }

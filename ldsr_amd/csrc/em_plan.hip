@@ -68,7 +68,7 @@ static bool conv_wide(double tol, int PP, int QQ) { return tol > 0.0 && PP + QQ 
 
 // does the LEAD form at lp lanes per cell fit a CU's LDS: the tail's image, the strips and the lead's u_t
 static bool lead_fits(int T, int tail, int PP, int QQ, int lp) {
-    const bool wide = PP > 4 || QQ > 4;
+    const bool wide = pair_wide(PP, QQ);
     int Lc = 0;
     long img = 0;
     em_pair_layout(tail, PP, QQ, lp, &Lc, &img, true);
@@ -116,7 +116,6 @@ EmPlan em_plan(const EmPlanIn &in) {
         return fail("bad (T, p, q, niter, tol)");
     const int T = in.T, PP = ldsr_pad_dim(in.p), QQ = ldsr_pad_dim(in.q);
     const double tol = in.tol;
-    const bool wide = PP > 4 || QQ > 4;
     pl.T = T; pl.PP = PP; pl.QQ = QQ;
     const bool was_auto = in.algo == LDSR_ALGO_AUTO;
     int &algo = pl.algo, &lpc = pl.lpc, &lead = pl.lead;     // (the plan's fields, worked on in place)
@@ -194,8 +193,9 @@ EmPlan em_plan(const EmPlanIn &in) {
     if (cpw) em_pair_layout(Te, PP, QQ, lpc, &pl.chunk, &img, lead > 0);
     // block table: static schedule (serial kernel; scan and pair kernels with tol == 0: every cell runs
     // exactly niter iterations) or per-series work queue (tol > 0: a wave whose cell converges early
-    // takes the next one instead of idling; wide LEAD forms: work-queue schedule only)
-    pl.queue = (algo == LDSR_ALGO_SCAN && scan_uses_queue(T, PP, QQ, tol)) || (cpw && (tol > 0.0 || (lead > 0 && wide)));
+    // takes the next one instead of idling; members without a static-schedule variant -- wide LEAD forms)
+    pl.queue = (algo == LDSR_ALGO_SCAN && scan_uses_queue(T, PP, QQ, tol)) ||
+               (cpw && (tol > 0.0 || !pair_variant(PP, QQ, pl.chunk, lpc, false, lead > 0)));
     pl.cpb = cells_per_block(algo, cpw ? Te : T, PP, QQ, lpc, cpw ? lead : 0);
     // steady form of the two-cells-per-wave kernel (fully observed series, chunks of >= 24 steps):
     // series_prep orders every series' cells by predicted slowness (em_pair_impl.h em_pair_body_steady)

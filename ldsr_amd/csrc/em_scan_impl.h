@@ -41,9 +41,7 @@
 // decision are bit-identical in all waves of the cell.
 //
 // Chunks longer than 16 steps keep J/g/h for their second half only and re-run the first half's
-// forward recursion before its backward sweep (register budget: two waves per SIMD).  Wide
-// inputs (padded p + q >= 12: nine or more LDS words per step) are compiled for one wave per
-// SIMD (512 registers) and carry e_t, B u_t from F1 to F2 in registers instead of re-forming them.
+// forward recursion before its backward sweep (register budget: two waves per SIMD).
 //
 // FIT: the same machinery run for exactly one E-step at the given thetas, writing the full fit
 // X, Y, V, J (Kalman_smoother, src/EM.cpp:22-131) and optionally penalized_likelihood
@@ -326,21 +324,7 @@ __host__ __device__ constexpr long scan_image_doubles(int L, int W, int PP, int 
 #define XCH_SUMS 40
 __host__ __device__ constexpr int scan_xch_doubles(int W) { return W > 1 ? W * (8 + 4 + XCH_SUMS) + 2 : 0; }
 
-// padded p + q >= 12: one wave per SIMD with the 512-register budget (LDSR_WIDE_OCC1), and
-// e_t / B u_t kept in registers from F1 to F2 (LDSR_WIDE_EBR); both switchable for A/B builds
-#ifndef LDSR_WIDE_OCC1
-#define LDSR_WIDE_OCC1 0
-#endif
-#ifndef LDSR_WIDE_EBR
-#define LDSR_WIDE_EBR 0
-#endif
-#ifndef LDSR_WIDE_SB      // scheduling barrier after every step of the wide kernels' sweeps
-#define LDSR_WIDE_SB 0
-#endif
-#ifndef LDSR_EB_ALIAS        // F1 hands e_t, B u_t to F2 through the (not yet live) g_t / h_t slots
-#define LDSR_EB_ALIAS 1
-#endif
-#ifndef LDSR_F2_BARRIER_EVERY   // scheduling barrier every n steps of F2 where the hand-over is on (0 = none)
+#ifndef LDSR_F2_BARRIER_EVERY   // scheduling barrier every n steps of F2 in the short chunks (F1's hand-over; 0 = none)
 #define LDSR_F2_BARRIER_EVERY 8
 #endif
 #ifndef LDSR_DENSE_F1_POW    // dense series: chunk composite = power of the 2x2 block + row recursion
@@ -351,12 +335,6 @@ __host__ __device__ constexpr int scan_xch_doubles(int W) { return W > 1 ? W * (
 #endif
 #ifndef LDSR_DENSE_F1_POW_MAXQ   // (8 since round 3: with the far LDS base the reversed read order no longer costs
 #define LDSR_DENSE_F1_POW_MAXQ 8  //  more than the flops save -- same box (4,8) -0.9 %, (2,8) -2.3 %, (1,8) -0.9 %)
-#endif
-#ifndef LDSR_GIMG_PREFETCH   // the same pipeline for the global image (same-box A/B: 2-5 % slower -- off)
-#define LDSR_GIMG_PREFETCH 0
-#endif
-#ifndef LDSR_SCAN_PREFETCH   // round 2's one-step pipeline of the LDS reads in the long-chunk sweeps (members without the
-#define LDSR_SCAN_PREFETCH 0  // ring below: it issues the next step's reads at the top of a step that then waits for its own -- off)
 #endif
 #ifndef LDSR_SCAN_SPF        // the image reads of the sweeps run a step or two ahead of their use (scan_spf below)
 #define LDSR_SCAN_SPF 1
@@ -373,7 +351,6 @@ __host__ __device__ constexpr int scan_xch_doubles(int W) { return W > 1 ? W * (
 #ifndef LDSR_SCAN_SPF_MAXPQ  // widest padded p + q that takes the read-ahead at every chunk length (register budget: two
 #define LDSR_SCAN_SPF_MAXPQ 8 // waves per SIMD); wider inputs -- the ring is ~50 VGPRs there -- only with chunks of <= 4 steps
 #endif
-__host__ __device__ constexpr bool scan_wide(int PP, int QQ) { return LDSR_WIDE_OCC1 && PP + QQ >= 12; }
 // Read-ahead of the series image in the sweeps (em_scan_cell: SPF).  Left alone the scheduler issues every
 // ds_read_b128 right before its use and waits for it.  Short chunks (<= 16 steps): with two waves per SIMD the
 // other wave covers that, a LONE wave -- the reference's own call shape, LDS_reconstruction(num.restarts = 50): 50
@@ -389,8 +366,6 @@ __host__ __device__ constexpr bool scan_spf(int PP, int QQ, int L, int W) {
     // one wave per cell, 17 .. 24 steps with padded p + q <= 10, 20 steps up to 12 (tools/resource_usage.py: no spills)
     return W == 1 && (L <= 4 || (LDSR_SCAN_SPF_WIDE_LONG && ((L > 16 && L <= 24 && PP + QQ <= 10) || (L == 20 && PP + QQ <= 12))));
 }
-__host__ __device__ constexpr bool scan_ebr(int PP, int QQ) { return LDSR_WIDE_EBR && PP + QQ >= 12; }
-__host__ __device__ constexpr bool scan_sb(int PP, int QQ) { return (LDSR_WIDE_SB || LDSR_WIDE_EBR) && PP + QQ >= 12; }
 
 // DENSE = every y_t of the series is observed: the per-step "observed ? a : b" selects vanish.
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -418,7 +393,7 @@ __device__ __forceinline__ void mark_cell_interrupted(const EmParams &prm, int c
 // GIMG = the series image is read from global memory instead of being copied to LDS.
 // W > 1: the workgroup is ONE group of W waves working on one cell at a time.
 template <int PP, int QQ, int L, int W, bool QUEUE, bool GIMG, bool FIT>
-__global__ __launch_bounds__(scan_wide(PP, QQ) ? 256 : 512) void em_scan_kernel(EmParams prm) {
+__global__ __launch_bounds__(512) void em_scan_kernel(EmParams prm) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr long IMG = scan_image_doubles(L, W, PP, QQ);
     const int b = blockIdx.x;
@@ -519,8 +494,6 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
                                              __amdgpu_buffer_rsrc_t rs, double *xch,
                                              int s, int cell, int lane, int wv, int nl, int rp, int &wit) {
     constexpr int NL = 64 * W;
-    constexpr bool EBR = scan_ebr(PP, QQ);    // e_t, B u_t stay in registers from F1 to F2
-    constexpr bool SB = scan_sb(PP, QQ);
     const int vl = wv * 64 + lane;            // virtual lane
     // element (step j, row k) of this lane's chunk of y / u / v
     // value i of step j of this lane (0 = y, 1.. = u, 1+PP.. = v): see the image layout above.
@@ -551,7 +524,7 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
     // SPF: the K values of a step are read SPFD steps ahead of their use into an explicit register ring pinned by
     // scheduling barriers (the full pairs of step j in slot j % SPFN; the odd value of an odd K comes in ONE
     // 16-byte read for the two steps 2 jj, 2 jj + 1 that share its pair: slot jj % OSL).
-    constexpr bool SPF = scan_spf(PP, QQ, L, W) && (!GIMG || (LDSR_SCAN_SPF_GIMG && PP + QQ <= LDSR_SCAN_SPF_MAXPQ)) && !scan_ebr(PP, QQ);
+    constexpr bool SPF = scan_spf(PP, QQ, L, W) && (!GIMG || (LDSR_SCAN_SPF_GIMG && PP + QQ <= LDSR_SCAN_SPF_MAXPQ));
     // (global image: an L2 round trip is several steps long)
     constexpr int SPFD = GIMG ? (scan_pairs(PP, QQ) <= 2 ? 3 : 2) : (scan_pairs(PP, QQ) <= 2 ? 2 : 1);
     constexpr int KH2 = 2 * (KV / 2);              // values held in full pairs
@@ -646,7 +619,6 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
     constexpr int HS = (L > 16) ? L / 2 : 0;   // L in {20, 24, 28, 32}
     constexpr int NS = L - HS;
     double Jv[NS], gv_[NS], hv[NS];
-    double ev[EBR ? L : 1], buv[EBR ? L : 1];
     // Short chunks (everything stored): F1 leaves e_t = y_t - D v_t and B u_t in the slots of
     // g_t / h_t, which are not live before F2 reaches step t -- F2 neither re-reads the series
     // from LDS nor re-forms the q + p products.  No extra registers on paper; in practice the
@@ -655,7 +627,7 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
     // VGPRs -- a scheduling barrier every 8 steps of F2 (LDSR_F2_BARRIER_EVERY) bounds that: no
     // spills on the narrow kernels, 21-23 on (4,8).  Same-box A/B of hand-over + barrier: cfg2
     // 1.537 -> 1.41 ms, cfg3 6.08 -> 5.24, cfg5 9.18 -> 8.47, masked (1,2) 1.71 -> 1.61.
-    constexpr bool EBA = (L <= 16) && !EBR && LDSR_EB_ALIAS;
+    constexpr bool EBA = L <= 16;
     double Jfin = 0.0;      // FIT: J[T-1] of src/EM.cpp:98 (the backward recursion itself uses 0)
 #ifdef LDSR_SCAN_TIMING
     unsigned long long tick_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -706,7 +678,6 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
         auto f1c = [&](int j, double e, double bu) {
             const bool o = DENSE || ((obsmask >> j) & 1u);
             if (SPF && j == L - 1) { eT = e; buT = bu; }
-            if constexpr (EBR) { ev[j] = e; buv[j] = bu; }
             if (EBA && j < L - 1) { gv_[j] = e; hv[j] = bu; }   // (the predicated L-th step re-reads)
             const double a00 = o ? alpha : A2;
             const double g = o ? C2R : 0.0;
@@ -717,7 +688,6 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
                 M = pstep(a00, Q, g, s20, bu, A, M);
             }
             if ((j & 15) == 15 && j < L - 2) prenorm(M);
-            if constexpr (SB) __builtin_amdgcn_sched_barrier(0);
         };
         auto f1 = [&](int j) { f1c(j, e_at(j), bu_at(j)); };
         if constexpr (DENSE && L <= 16 && PP <= LDSR_DENSE_F1_POW_MAXP && QQ <= LDSR_DENSE_F1_POW_MAXQ && LDSR_DENSE_F1_POW) {
@@ -812,7 +782,7 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
                     __builtin_amdgcn_sched_barrier(0x6);
                 }
                 if (tail) f1c(L - 1, e_of(r.w[(L - 1) % SPFN], r.o, L - 1), bu_of(r.w[(L - 1) % SPFN], r.o, L - 1));
-            } else if (L <= 16 || EBR) {
+            } else if (L <= 16) {
 #pragma unroll
                 for (int j = 0; j < L - 1; j++) f1(j);
             } else {           // no register arrays here: keep long chunks rolled (code size, VGPRs)
@@ -893,12 +863,6 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
         double r0 = fast_rcp(sg);
         const double Xp0 = Xp, Vp0 = Vp, sg0 = sg, r00 = r0;   // entry state (re-run of [0, HS))
         double Pi = 1.0, G = 0.0, H = 0.0;                     // reverse composite (HS > 0 only)
-        // Long chunks end every step with a scheduling barrier (register pressure), which would
-        // also pin each step's LDS reads right before their use: software-pipeline them one step
-        // ahead instead (PF) -- the reads of step j+1 are issued at the top of step j.
-        constexpr bool PF = L > 16 && !EBR && (LDSR_SCAN_PREFETCH || (GIMG && LDSR_GIMG_PREFETCH));
-        double e_nx = 0.0, bu_nx = 0.0;
-        if (PF && act) { e_nx = e_at(0); bu_nx = bu_at(0); }
         auto f2c = [&](int j, double e, double bu) {
             const bool o = DENSE || ((obsmask >> j) & 1u);
             const double r = o ? r0 : 0.0;             // 1/Sigma_t; 0 = "no update" (:82-84)
@@ -944,23 +908,16 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
             }
             Xp = Xp1;
             Vp = Vp1;
-            if (L > 16 || SB) __builtin_amdgcn_sched_barrier(0);
+            if (L > 16) __builtin_amdgcn_sched_barrier(0);   // (long chunks: register pressure)
             if (EBA && LDSR_F2_BARRIER_EVERY > 0 && (j % LDSR_F2_BARRIER_EVERY) == LDSR_F2_BARRIER_EVERY - 1)
                 __builtin_amdgcn_sched_barrier(0);
         };
+        // (with the ring, SPF, long chunks do not come here: eT, buT are asked for in short chunks only, at step L-1)
         auto f2 = [&](int j) {
             double e, bu;
-            if constexpr (PF) {
-                e = e_nx; bu = bu_nx;
-                if (j + 1 < L) { e_nx = e_at(j + 1); bu_nx = bu_at(j + 1); }
-            } else if (EBA && j < L - 1) {
-                e = gv_[j]; bu = hv[j];                // left there by F1; overwritten below by g_t, h_t
-            } else if (SPF) {
-                e = eT; bu = buT;                      // (the predicated step: kept by F1)
-            } else {
-                e = EBR ? ev[j] : e_at(j);
-                bu = EBR ? buv[j] : bu_at(j);
-            }
+            if (EBA && j < L - 1) { e = gv_[j]; bu = hv[j]; }     // handed over by F1; overwritten below by g_t, h_t
+            else if (SPF) { e = eT; bu = buT; }                   // the predicated last step: kept by F1
+            else { e = e_at(j); bu = bu_at(j); }                  // read from the image
             f2c(j, e, bu);
         };
         if (act) {
@@ -1116,7 +1073,7 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
                 const double d = Xnx - fma(th.A, Xs, bu);
                 aSsq = fin ? aSsq : fma(d, d, aSsq);
             }
-            if ((L > 16 && (j & 3) == 3) || SB) __builtin_amdgcn_sched_barrier(0);
+            if (L > 16 && (j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         };
         auto b2b = [&](int j, int i, bool top) { b2b_v(j, i, top, [&](int k) { return val(j, k); }); };
         if (act) {
@@ -1173,7 +1130,6 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
             // re-run the forward recursion of steps [0, HS) from the lane's entry state; the
             // likelihood terms of these steps were already accumulated in F2
             double Xq = Xp0, Vq = Vp0, sgq = sg0, rq = r00;
-            if (PF && act) { e_nx = e_at(0); bu_nx = bu_at(0); }
             auto f2rc = [&](int j, double e, double bu) {
                 const bool o = DENSE || ((obsmask >> j) & 1u);
                 const double r = o ? rq : 0.0;
@@ -1199,17 +1155,7 @@ __device__ __forceinline__ bool em_scan_cell(const EmParams &prm, const double *
                 Vq = Vp1;
                 __builtin_amdgcn_sched_barrier(0);   // keep later steps' LDS loads from being hoisted (VGPR pressure)
             };
-            auto f2r = [&](int j) {
-                double e, bu;
-                if constexpr (PF) {
-                    e = e_nx; bu = bu_nx;
-                    if (j + 1 < HS) { e_nx = e_at(j + 1); bu_nx = bu_at(j + 1); }
-                } else {
-                    e = EBR ? ev[j] : e_at(j);
-                    bu = EBR ? buv[j] : bu_at(j);
-                }
-                f2rc(j, e, bu);
-            };
+            auto f2r = [&](int j) { f2rc(j, e_at(j), bu_at(j)); };     // (without the ring: read from the image)
             if (act) {
                 if constexpr (SPF) {
                     StepRing r;
@@ -1372,6 +1318,15 @@ __host__ __device__ constexpr bool scan_image_fits_lds(int L, int W, int PP, int
 }
 __host__ __device__ constexpr bool scan_uses_gimg(int L, int W, int PP, int QQ) {
     return L >= 20 && (W > 1 || !scan_image_fits_lds(L, W, PP, QQ));
+}
+// Which instantiations of a member exist, for the launcher (em_scan_launch.inc) and the inventory
+// (kernels_scan.hip) alike.  Global-image form: work queue and FIT; LDS form (one wave per cell only):
+// static schedule, work queue and FIT.
+__host__ __device__ constexpr bool scan_variant(int PP, int QQ, int L, int W, bool queue, bool gimg, bool fit) {
+    if (queue && fit) return false;       // (FIT: one E-step per cell, nothing to balance)
+    const bool g = scan_uses_gimg(L, W, PP, QQ);
+    if (gimg) return g && (queue || fit);
+    return !g && W == 1 && scan_image_fits_lds(L, W, PP, QQ);
 }
 
 // Launch plan of a (T, PP, QQ) shape: chunk length, waves per cell, cells per workgroup, and

@@ -1,50 +1,35 @@
-// em_scan_launch.inc -- included by em_scan_L*.hip with SCAN_L (and optionally SCAN_W) defined:
-// instantiates the scan kernel for every padded (PP, QQ) at that chunk length / wave count and
-// defines its launcher.  Variants per shape: static schedule, work queue, FIT (one E-step, full
-// fit written out); global-image forms of them for L >= 20.  Multi-wave cells (W > 1) exist with
-// the queue schedule and as FIT only, always on the global image.
+// em_scan_launch.inc -- the translation unit of one scan member (em_members.h), compiled with -DSCAN_L=<L>
+// -DSCAN_W=<W>: instantiates the scan kernel for every padded (PP, QQ) at that chunk length / wave count in
+// the variants scan_variant() names (em_scan_impl.h) and defines the member's launcher.
 #include "em_scan_impl.h"
 #include "ldsr_kernels.h"
-
-#ifndef SCAN_W
-#define SCAN_W 1
-#endif
 
 template <int PP, int QQ, bool QUEUE, bool GIMG, bool FIT>
 static hipError_t launch_v(const EmParams &prm, int n_blocks, int cpb, hipStream_t stream) {
     constexpr int L = SCAN_L, W = SCAN_W;
-    const size_t lds = ((GIMG ? 0 : (size_t)scan_image_doubles(L, W, PP, QQ)) + scan_xch_doubles(W)) * sizeof(double);
-    auto kern = em_scan_kernel<PP, QQ, L, W, QUEUE, GIMG, FIT>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+    if constexpr (scan_variant(PP, QQ, L, W, QUEUE, GIMG, FIT)) {
+        const size_t lds = ((GIMG ? 0 : (size_t)scan_image_doubles(L, W, PP, QQ)) + scan_xch_doubles(W)) * sizeof(double);
+        auto kern = em_scan_kernel<PP, QQ, L, W, QUEUE, GIMG, FIT>;
+        if (lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void *)kern,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * W * cpb), lds, stream, prm);
+        return hipGetLastError();
     }
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * W * cpb), lds, stream, prm);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
+// (launch_em_scan hands over a schedule the image form has: FIT without the queue, the global image with it)
 template <int PP, int QQ>
 static hipError_t launch_one(const EmParams &prm, int n_blocks, int cpb, bool queue, bool gimg,
                              bool fit, hipStream_t stream) {
-    constexpr int L = SCAN_L, W = SCAN_W;
-    // a member exists in the form the plan uses (scan_plan) and in no other: global image where the LDS
-    // cannot hold it (L >= 20) and for multi-wave cells, LDS image everywhere else
-    constexpr bool GIMG_FORM = scan_uses_gimg(L, W, PP, QQ);
-    constexpr bool LDS_FORM = !GIMG_FORM && W == 1 && scan_image_fits_lds(L, W, PP, QQ);
-    if (gimg) {
-        if constexpr (GIMG_FORM) {
-            return fit ? launch_v<PP, QQ, false, true, true>(prm, n_blocks, cpb, stream)
-                       : launch_v<PP, QQ, true, true, false>(prm, n_blocks, cpb, stream);
-        }
-        return hipErrorInvalidValue;
-    }
-    if constexpr (LDS_FORM) {
-        if (fit) return launch_v<PP, QQ, false, false, true>(prm, n_blocks, cpb, stream);
-        if (queue) return launch_v<PP, QQ, true, false, false>(prm, n_blocks, cpb, stream);
-        return launch_v<PP, QQ, false, false, false>(prm, n_blocks, cpb, stream);
-    }
-    return hipErrorInvalidValue;
+    if (fit) return gimg ? launch_v<PP, QQ, false, true, true>(prm, n_blocks, cpb, stream)
+                         : launch_v<PP, QQ, false, false, true>(prm, n_blocks, cpb, stream);
+    if (gimg) return launch_v<PP, QQ, true, true, false>(prm, n_blocks, cpb, stream);
+    return queue ? launch_v<PP, QQ, true, false, false>(prm, n_blocks, cpb, stream)
+                 : launch_v<PP, QQ, false, false, false>(prm, n_blocks, cpb, stream);
 }
 
 template <>

@@ -1,10 +1,11 @@
 // kernels_scan.hip -- launch plan of the parallel-in-time scan kernel (chunk length L, waves
 // per cell W, LDS or global series image) and dispatch to the per-(L, W) translation units
-// (em_scan_L*.hip).
+// (em_members.h).
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 
+#include "em_members.h"
 #include "em_scan_impl.h"
 #include "em_pair_impl.h"
 #include "ldsr_kernels.h"
@@ -13,7 +14,6 @@ static const size_t kLdsBytes = 160 * 1024;
 
 // waves per block so that a CU holds ~8 waves given the LDS image of one series
 static int scan_wpb(int L, int PP, int QQ) {
-    if (scan_wide(PP, QQ)) return 4;      // one wave per SIMD (512-register kernels)
     const size_t lds = (size_t)scan_image_doubles(L, 1, PP, QQ) * sizeof(double);
     const int blocks_per_cu = (int)(kLdsBytes / lds);
     const int want = 8;
@@ -24,22 +24,16 @@ static int scan_wpb(int L, int PP, int QQ) {
     return wpb > cap ? cap : wpb;
 }
 
-// W = 1: smallest compiled chunk length with T <= 64 L (every choice also has L (L-1) <= T).
+// Smallest compiled chunk length (em_members.h) of the wave count W with T <= 64 W L.
+// W = 1: every choice also has L (L-1) <= T.
 // T > 2048: W = 2 (T <= 4096) or 4 (T <= 8192) waves per cell with half-stored chunks.
 ScanPlan scan_plan(int T, int PP, int QQ) {
     ScanPlan p;
     if (PP > 8 || QQ > 8 || T < 2) return p;   // instantiated for padded widths up to 8
-    static const int Ls[] = {2, 3, 4, 6, 8, 10, 12, 13, 14, 15, 16, 20, 24, 28, 32};
-    static const int LsW[] = {20, 24, 28, 32};
-    if (T <= 2048) {
-        p.W = 1;
-        for (int L : Ls)
-            if (T <= 64 * L) { p.L = (T >= L * (L - 1)) ? L : 0; break; }
-    } else if (T <= 8192) {
-        p.W = T <= 4096 ? 2 : 4;
-        for (int L : LsW)
-            if (T <= 64 * p.W * L) { p.L = L; break; }
-    }
+    if (T > 8192) return p;
+    p.W = T <= 2048 ? 1 : T <= 4096 ? 2 : 4;
+    for (const EmMember &m : kScanMembers)
+        if (m.n == p.W && T <= 64 * p.W * m.L) { p.L = (p.W > 1 || T >= m.L * (m.L - 1)) ? m.L : 0; break; }
     if (!p.L) return p;
     // the image is read from global memory (raw buffer loads, L2 / L1 resident) when it does not
     // fit a CU's LDS (L >= 20 only: the short-chunk images always fit) and for every multi-wave
@@ -82,11 +76,7 @@ hipError_t launch_em_scan(const EmParams &prm, int PP, int QQ, int n_blocks, boo
 #define CASE_LW(Lv, Wv) \
     case Lv * 8 + Wv: return launch_em_scan_LW<Lv, Wv>(prm, PP, QQ, n_blocks, p.cpb, queue, p.gimg, fit, stream);
     switch (p.L * 8 + p.W) {
-        CASE_LW(2, 1) CASE_LW(3, 1) CASE_LW(4, 1) CASE_LW(6, 1) CASE_LW(8, 1) CASE_LW(10, 1)
-        CASE_LW(12, 1) CASE_LW(13, 1) CASE_LW(14, 1) CASE_LW(15, 1) CASE_LW(16, 1)
-        CASE_LW(20, 1) CASE_LW(24, 1) CASE_LW(28, 1) CASE_LW(32, 1)
-        CASE_LW(20, 2) CASE_LW(24, 2) CASE_LW(28, 2) CASE_LW(32, 2)
-        CASE_LW(20, 4) CASE_LW(24, 4) CASE_LW(28, 4) CASE_LW(32, 4)
+        LDSR_SCAN_MEMBERS(CASE_LW)
         default: return hipErrorInvalidValue;
     }
 #undef CASE_LW
@@ -105,14 +95,15 @@ PairPlan pair_plan(int T, int PP, int QQ, int lpc, bool lead_form) {
     // Wide inputs (padded p or q = 8) exist as the two-cells-per-wave LEAD form only: the tail of a
     // closed-form lead in chunks of <= 16 steps (the generic sweeps of long chunks do not fit the
     // registers of two waves per SIMD at q = 8; the lead itself never touches v_t).
-    const bool wide = PP > 4 || QQ > 4;
+    const bool wide = pair_wide(PP, QQ);
     if ((lpc != 32 && lpc != 16) || PP > 8 || QQ > 8 || T <= 64) return p;
     if (wide && !(lead_form && ((lpc == 32 && T <= 512) || (lpc == 16 && T <= 256)))) return p;
-    if (lead_form && T > lpc * 16) return p;      // (LEAD forms: chunks of <= 16 steps)
-    // every chunk length from 3 to 32: the shortest one wastes no lanes (four cells per wave: from 5)
+    if (lead_form && T > lpc * kPairLeadMaxL) return p;
+    // every compiled chunk length (em_members.h: 3 to 32, four cells per wave from 5): the shortest one wastes no lanes
     // (lanes 0 .. rp-1 own L steps, the others L-1: needs 1 <= rp <= nl)
-    for (int L = (lpc == 16 ? 5 : 3); L <= 32; L++) {
-        if (T > lpc * L) continue;
+    for (const EmMember &m : kPairMembers) {
+        const int L = m.L;
+        if (m.n != lpc || T > lpc * L) continue;
         const int nl = (T + L - 1) / L, rp = T - nl * (L - 1);
         if (rp >= 1 && rp <= nl) { p.L = L; break; }
     }
@@ -163,14 +154,10 @@ hipError_t launch_em_pair(const EmParams &prm, int PP, int QQ, int lpc, int n_bl
     PairPlan p = pair_plan(prm.T - prm.lead, PP, QQ, lpc, prm.lead > 0);     // (LEAD form: the tail's plan)
     if (!p.ok || !prm.img2 || (prm.lead > 0 && !prm.img3)) return hipErrorInvalidValue;
     p.wpb = em_pair_waves_per_block(prm.T - prm.lead, PP, QQ, lpc, prm.lead);
-#define CASE_L(Lv) case Lv: return lpc == 32 ? launch_em_pair_L<Lv, 32>(prm, PP, QQ, n_blocks, p.wpb, queue, stream) \
-                                             : launch_em_pair_L<Lv, 16>(prm, PP, QQ, n_blocks, p.wpb, queue, stream);
-    switch (p.L) {
-        case 3: return launch_em_pair_L<3, 32>(prm, PP, QQ, n_blocks, p.wpb, queue, stream);
-        case 4: return launch_em_pair_L<4, 32>(prm, PP, QQ, n_blocks, p.wpb, queue, stream);
-        CASE_L(5) CASE_L(6) CASE_L(7) CASE_L(8) CASE_L(9) CASE_L(10) CASE_L(11) CASE_L(12) CASE_L(13) CASE_L(14)
-        CASE_L(15) CASE_L(16) CASE_L(17) CASE_L(18) CASE_L(19) CASE_L(20) CASE_L(21) CASE_L(22) CASE_L(23)
-        CASE_L(24) CASE_L(25) CASE_L(26) CASE_L(27) CASE_L(28) CASE_L(29) CASE_L(30) CASE_L(31) CASE_L(32)
+#define CASE_L(Lv, LPCv) \
+    case Lv * 64 + LPCv: return launch_em_pair_L<Lv, LPCv>(prm, PP, QQ, n_blocks, p.wpb, queue, stream);
+    switch (p.L * 64 + lpc) {
+        LDSR_PAIR_MEMBERS(CASE_L)
         default: return hipErrorInvalidValue;
     }
 #undef CASE_L
@@ -178,47 +165,31 @@ hipError_t launch_em_pair(const EmParams &prm, int PP, int QQ, int lpc, int n_bl
 
 
 // ---- what is compiled ------------------------------------------------------------------------------
-// Every instantiation of the scan and pair families this library holds, by the names rocprofv3 prints,
-// derived from the SAME predicates the launchers instantiate with (em_scan_launch.inc launch_one,
-// em_pair_launch.inc): tests/test_abi_and_host.py checks that this set equals what the launch plans can
+// Every instantiation of the scan and pair families this library holds, by the names rocprofv3 prints:
+// the members of em_members.h in the variants scan_variant() / pair_variant() name -- the list the build
+// and the launchers are made of and the predicates the launchers instantiate with.  tests/test_abi_and_host.py
+// checks that this set equals the kernels in the built library's code objects AND what the launch plans can
 // return over the supported domain -- nothing unreachable is compiled, nothing reachable is missing.
 void em_kernel_inventory(std::string &out) {
     static const int widths[] = {1, 2, 4, 8};
-    static const int Ls1[] = {2, 3, 4, 6, 8, 10, 12, 13, 14, 15, 16, 20, 24, 28, 32};
-    static const int LsW[] = {20, 24, 28, 32};
+    static const char *const tf[] = {"false", "true"};
     char buf[160];
-    auto scan_names = [&](int L, int W) {
+    for (const EmMember &m : kScanMembers)
         for (int PP : widths)
-            for (int QQ : widths) {
-                const bool gimg = scan_uses_gimg(L, W, PP, QQ);
-                const bool lds = !gimg && W == 1 && scan_image_fits_lds(L, W, PP, QQ);
-                auto add = [&](bool q, bool g, bool f) {
-                    snprintf(buf, sizeof(buf), "em_scan_kernel<%d, %d, %d, %d, %s, %s, %s>\n", PP, QQ, L, W,
-                             q ? "true" : "false", g ? "true" : "false", f ? "true" : "false");
+            for (int QQ : widths)
+                for (int v = 0; v < 8; v++) {
+                    const bool q = v & 1, g = v & 2, f = v & 4;
+                    if (!scan_variant(PP, QQ, m.L, m.n, q, g, f)) continue;
+                    snprintf(buf, sizeof(buf), "em_scan_kernel<%d, %d, %d, %d, %s, %s, %s>\n", PP, QQ, m.L, m.n, tf[q], tf[g], tf[f]);
                     out += buf;
-                };
-                if (gimg) { add(true, true, false); add(false, true, true); }
-                if (lds) { add(false, false, false); add(true, false, false); add(false, false, true); }
-            }
-    };
-    for (int L : Ls1) scan_names(L, 1);
-    for (int W : {2, 4})
-        for (int L : LsW) scan_names(L, W);
-    for (int lpc : {32, 16})
-        for (int L = (lpc == 16 ? 5 : 3); L <= 32; L++)
-            for (int PP : widths)
-                for (int QQ : widths) {
-                    if (!pair_member_fits(L, lpc, PP, QQ)) continue;
-                    const bool wide = PP > 4 || QQ > 4;
-                    auto add = [&](bool q, bool lead) {
-                        snprintf(buf, sizeof(buf), "em_pair_kernel<%d, %d, %d, %d, %s, %s>\n", PP, QQ, L, lpc,
-                                 q ? "true" : "false", lead ? "true" : "false");
-                        out += buf;
-                    };
-                    if (!wide) { add(false, false); add(true, false); }
-                    if (L <= 16) {                       // LEAD forms: chunks of <= 16 steps
-                        if (!wide) add(false, true);
-                        add(true, true);                 // (wide inputs: LEAD form, work-queue schedule only)
-                    }
+                }
+    for (const EmMember &m : kPairMembers)
+        for (int PP : widths)
+            for (int QQ : widths)
+                for (int v = 0; v < 4; v++) {
+                    const bool q = v & 1, lead = v & 2;
+                    if (!pair_variant(PP, QQ, m.L, m.n, q, lead)) continue;
+                    snprintf(buf, sizeof(buf), "em_pair_kernel<%d, %d, %d, %d, %s, %s>\n", PP, QQ, m.L, m.n, tf[q], tf[lead]);
+                    out += buf;
                 }
 }

@@ -53,6 +53,41 @@ def test_code_object_is_gfx950_only():
     assert n >= 50 and triples == {b"gfx950"}, (n, triples)
 
 
+def test_inventory_names_exactly_the_kernels_in_the_library():
+    """ldsr_kernel_inventory() is derived from the member table (ldsr_amd/csrc/em_members.h) and the
+    variant rules the launchers instantiate with; this test reads the kernel symbols of every code object
+    of the built library (tools/kernel_digest.py) and asserts that its em_scan_kernel / em_pair_kernel
+    instantiations are the inventory's names, no more and no fewer.  With
+    test_library_holds_exactly_the_kernels_a_plan_can_return: plan -> inventory -> binary."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_digest
+    from ldsr_amd import _lib
+    L = _lib.lib()
+    n = L.ldsr_kernel_inventory(None, 0)
+    buf = C.create_string_buffer(n)
+    L.ldsr_kernel_inventory(buf, n)
+    inventory = [l for l in buf.value.decode().split("\n") if l]
+    assert len(inventory) == len(set(inventory)) > 1000
+
+    mangled = set()
+    for elf in kernel_digest.code_objects(_lib.SO_PATH):
+        mangled |= set(name for name, _, kd in kernel_digest.functions(elf) if kd)
+    mangled = sorted(mangled)
+
+    def spelled_like_the_inventory(name):     # "void em_scan_kernel<1, 2, 16, 1, false, false, false>(EmParams)"
+        name = re.sub(r"^void ", "", name)
+        name = re.sub(r"\(EmParams\)$", "", name)
+        name = re.sub(r"\(bool\)([01])", lambda m: ("false", "true")[int(m.group(1))], name)
+        return re.sub(r"\s*,\s*", ", ", name)
+
+    binary = [spelled_like_the_inventory(k) for k in kernel_digest.demangle(mangled)]
+    binary = [k for k in binary if k.startswith(("em_scan_kernel<", "em_pair_kernel<"))]
+    assert len(binary) == len(set(binary))
+    assert sorted(set(binary) - set(inventory)) == [], "in the library, not in the inventory"
+    assert sorted(set(inventory) - set(binary)) == [], "in the inventory, not in the library"
+
+
 def test_argument_validation_without_gpu():
     from ldsr_amd import _lib
     L = _lib.lib()

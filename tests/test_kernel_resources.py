@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 def test_scan_kernel_register_budget():
     import resource_usage
-    rows = {r[0]: r for r in resource_usage.table(os.path.join(ROOT, "ldsr_amd", "csrc", "em_scan_L16.hip"))}
+    rows = {r[0]: r for r in resource_usage.table("em_scan_16_1")}
     assert len(rows) == 48      # 16 padded (p, q) shapes x {static, queue, FIT}
 
     def get(name):
@@ -77,10 +77,10 @@ def test_pair_kernel_register_budget():
     the four-cells-per-wave kernel of a short series, and the LEAD forms of configs 4 and 5: two waves per SIMD and no scratch (the first
     cut of the pair kernel spilled 73 VGPRs until the reverse composite moved into F2)."""
     import resource_usage
-    for tu, tmpl in (("em_pair_L23.hip", "<1, 2, 23, 32, false, false>"), ("em_pair_L23.hip", "<1, 2, 23, 32, true, false>"),
-                     ("em_pair_L23.hip", "<1, 4, 23, 32, false, false>"), ("em_quad_L13.hip", "<1, 2, 13, 16, false, false>"),
-                     ("em_quad_L13.hip", "<1, 4, 13, 16, false, true>"), ("em_quad_L6.hip", "<1, 4, 6, 16, false, true>")):
-        rows = resource_usage.table(os.path.join(ROOT, "ldsr_amd", "csrc", tu), tmpl)
+    for tu, tmpl in (("em_pair_23_32", "<1, 2, 23, 32, false, false>"), ("em_pair_23_32", "<1, 2, 23, 32, true, false>"),
+                     ("em_pair_23_32", "<1, 4, 23, 32, false, false>"), ("em_pair_13_16", "<1, 2, 13, 16, false, false>"),
+                     ("em_pair_13_16", "<1, 4, 13, 16, false, true>"), ("em_pair_6_16", "<1, 4, 6, 16, false, true>")):
+        rows = resource_usage.table(tu, tmpl)
         assert len(rows) == 1, (tu, tmpl, [r[0] for r in rows])
         _, vgpr, agpr, vspill, scratch, occ, sgpr, sspill = rows[0]
         assert (vspill, scratch) == (0, 0) and occ >= 2 and vgpr <= 256, (tu, tmpl, vgpr, vspill, scratch, occ)

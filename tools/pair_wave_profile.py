@@ -1,5 +1,5 @@
 """Per-wave time of BASELINE config 2's launch (GPU box; library built with -DLDSR_SCAN_TIMING:
-tools/build_variant.sh timing "-DLDSR_SCAN_TIMING" em_pair_L32): the kernel's time is its slowest
+tools/build_variant.sh timing "-DLDSR_SCAN_TIMING" em_pair_32_32): the kernel's time is its slowest
 wave's, so print the distribution over waves, what the slowest spent in the generic sweeps, and the
 shader clock.  niter = 100, tol = 0 by default; --tol 1e-5 --niter 1000 for the converged run."""
 import argparse

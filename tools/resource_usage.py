@@ -1,15 +1,30 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of every kernel in a HIP translation unit (gfx950):
-    python tools/resource_usage.py ldsr_amd/csrc/em_scan_L16.hip [name-filter]
+    python tools/resource_usage.py em_scan_16_1 [name-filter]
+    python tools/resource_usage.py ldsr_amd/csrc/kernels_serial.hip [name-filter]
 Parses hipcc -Rpass-analysis=kernel-resource-usage (no GPU needed)."""
+import os
 import re
 import subprocess
 import sys
 
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ldsr_amd", "csrc")
 
-def table(src, flt=""):
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-           "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
+
+def unit_source(unit):
+    """compiler arguments that name a translation unit: a source file, or a member of the EM kernel families
+    by the name of its object -- em_scan_<L>_<W>, em_pair_<L>_<LPC> (ldsr_amd/csrc/em_members.h, Makefile)"""
+    m = re.fullmatch(r"em_(scan|pair)_(\d+)_(\d+)", unit)
+    if not m:
+        return [unit]
+    first, second = ("SCAN_L", "SCAN_W") if m.group(1) == "scan" else ("PAIR_L", "PAIR_LPC")
+    return ["-D%s=%s" % (first, m.group(2)), "-D%s=%s" % (second, m.group(3)), "-x", "hip",
+            os.path.join(CSRC, "em_%s_launch.inc" % m.group(1))]
+
+
+def table(unit, flt=""):
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function",
+           "-Rpass-analysis=kernel-resource-usage", "-c"] + unit_source(unit) + ["-o", "/dev/null"]
     txt = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows = []
     for b in re.split(r"remark: Function Name: ", txt)[1:]:

@@ -1,5 +1,5 @@
 """Where does ONE wave's EM iteration go?  (GPU box; library built with -DLDSR_SCAN_TIMING, see
-em_scan_impl.h: tools/build_variant.sh timing "-DLDSR_SCAN_TIMING" em_scan_L2 em_scan_L4 em_scan_L13)
+em_scan_impl.h: tools/build_variant.sh timing "-DLDSR_SCAN_TIMING" em_scan_2_1 em_scan_4_1 em_scan_13_1)
 
 Prints shader-clock cycles per iteration of every section of the scan kernel for the small-launch
 shapes of profiles/r03_small_launches.txt (lone waves: the launch's time is one wave's latency)."""
