@@ -24,6 +24,11 @@
  *   ldsr_mstep_batch         _ldsr_Mstep (src/RcppExports.cpp:26-38 -> src/EM.cpp:139-229)
  *   ldsr_propagate_batch     _ldsr_propagate (src/RcppExports.cpp:56-69 -> src/EM.cpp:295-356)
  *   ldsr_penalized_lik_batch penalized_likelihood of R/LDS_GA.R:28-44 for a whole GA population
+ *   ldsr_ga_batch            LDS_GA (R/LDS_GA.R:54-82): the whole island GA -- fitness, selection,
+ *                            crossover, mutation, elitism, migration, the stop rule -- for one series
+ *                            or the folds of cvLDS(method = "GA") in ONE call; the population never
+ *                            leaves HBM.  An island GA of GA::gaisl's family by this project's own
+ *                            specification, NOT gaisl's random stream
  *   ldsr_select_restart      the argmax-with-C>0 rule of R/LDS_reconstruction.R:50-58
  *   ldsr_simulate_batch      LDS_rep / one_LDS_rep (R/stochastics.R:18-63): num_reps stochastic
  *                            replicates of each of n_models thetas in one launch; with the uniforms
@@ -238,6 +243,41 @@ int ldsr_penalized_lik_batch(int device, int n_series, int T, int p, int q, cons
                              const double *u, const double *v, int shared_uv,
                              const int *cell_offsets, const double *theta, double lambda,
                              double *pl);
+
+/* LDS_GA (R/LDS_GA.R:54-82): an island genetic algorithm that maximises penalized_likelihood over
+ * packed thetas inside the box [lb, ub], entirely on the device.  The algorithm -- operators, stop rule,
+ * the layout of the counter-mode random streams -- is specified in INTEGRATION.md ("The island GA");
+ * it is of the family of GA::gaisl, which the reference calls, and does not reproduce gaisl's stream.
+ * n_series independent problems (the folds of cvLDS: shared_uv) run side by side, each with num_islands
+ * islands of pop_per_island individuals (2 .. LDSR_GA_MAX_POP); problem s draws under seed + s, so it
+ * evolves exactly as problem 0 of a one-problem call with that seed, whatever else shares the call.
+ *   lb, ub       [6+p+q] finite, lb <= ub           lambda   the penalty weight of R/LDS_GA.R:41
+ *   maxiter      generations at most (>= 1)         run      stop after this many generations without
+ *                                                            a new best (>= 1; the reference: 100)
+ *   suggestions  [n_series][n_suggestions][6+p+q] or NULL: the first individuals of island 0, clipped
+ *                to the box (n_suggestions <= pop_per_island)
+ *   theta_best   [n_series][6+p+q]   pl_best [n_series] (-inf, theta NaN: no finite fitness ever)
+ *   n_gen        [n_series] generations evaluated
+ *   trace        [n_series][maxiter] best so far after each generation, NaN beyond n_gen; may be NULL
+ *   population   [n_series][num_islands][pop_per_island][6+p+q], fitness [n_series][num_islands]
+ *                [pop_per_island]: the LAST EVALUATED generation (index n_gen - 1) and its fitness;
+ *                each may be NULL
+ * Host pointers.  The series are uploaded and prepared once; a generation is two launches (the
+ * smoother's scalar-only pass, then breeding), enqueued LDSR_GA_CHUNK generations at a time with one
+ * small read-back in between; the interrupt callback is polled there (LDSR_EINTERRUPTED).  One problem of
+ * the reference's default size is 400 cells and cannot fill the device: batch problems into one call. */
+#define LDSR_GA_MAX_POP 1024
+#define LDSR_GA_PCROSSOVER 0.8          /* probability that a selected pair is crossed */
+#define LDSR_GA_PMUTATION 0.1           /* probability that a child has one gene redrawn */
+#define LDSR_GA_ELITE_PCT 5             /* elites: max(1, (5 n + 50) / 100), 5 % rounded half up */
+#define LDSR_GA_MIGRATION_PCT 10        /* migrants: max(1, 10 n / 100), 10 % rounded down */
+#define LDSR_GA_MIGRATION_INTERVAL 10   /* migrate after every 10th generation */
+#define LDSR_GA_CHUNK 32                /* generations enqueued between two looks at the stop flags */
+int ldsr_ga_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                  const double *v, int shared_uv, const double *lb, const double *ub, double lambda,
+                  int num_islands, int pop_per_island, int maxiter, int run, unsigned long long seed,
+                  const double *suggestions, int n_suggestions, double *theta_best, double *pl_best,
+                  int *n_gen, double *trace, double *population, double *fitness);
 
 /* Stochastic replicates: one_LDS_rep / LDS_rep (R/stochastics.R:18-63) for n_models thetas x
  * num_reps replicates of T steps,

@@ -52,6 +52,9 @@ SIGNATURES = {
                                        C.c_int, _ip, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "ldsr_penalized_lik_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                            C.c_int, _ip, _dp, C.c_double, _dp]),
+    "ldsr_ga_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, C.c_int,
+                                _dp, _dp, _ip, _dp, _dp, _dp]),
     "ldsr_simulate_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp,
                                       _dp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, _dp, _dp, _dp]),
     "ldsr_simulate_draw_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int,

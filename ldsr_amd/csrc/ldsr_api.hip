@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,7 @@
 #include "../../include/ldsr_hip.h"
 #include "ldsr_kernels.h"
 #include "em_pair_impl.h"      // (layout constants only)
+#include "ga.h"
 #include "source_hash.h"       // LDSR_SOURCE_HASH, written by the Makefile
 
 static thread_local std::string g_err;
@@ -720,38 +722,60 @@ extern "C" int ldsr_em_batch_device(int device, void *stream_, int n_series, int
 
 // One Kalman_smoother pass (src/EM.cpp:22-131) for n cells on prepared series: the FIT form of
 // the scan kernel (one wave group per cell) whenever the shape is supported, else the serial
-// one-thread-per-cell kernel.  blk_*: host block table rows (series, first cell, cells) of the
-// scan launch; it travels through the pinned staging ring.  d_tab: device room for 3*n_blocks
-// ints.  mode: 0 smoother, 1 propagate (serial kernel only).
-static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, int PP, int QQ,
-                           bool has_u, bool has_v, int shared_uv, char *ws, const WsLayout &L,
-                           int n, const std::vector<int> &series_of_cell, const double *d_theta,
-                           int stdlik, int mode, double lambda, double *d_X, double *d_Y,
-                           double *d_V, double *d_J, double *d_lik, double *d_pen, int *d_status,
-                           int *d_soc, bool scalar_only, const int *d_tab_prebuilt = nullptr) {
-    if (mode == 0 && L.img_stride && em_scan_supported(T, PP, QQ)) {
-        const int cpb = em_scan_cells_per_block(T, PP, QQ);
-        const int *d_tab = d_tab_prebuilt;      // [3][n]: one block per cell, filled on the device
-        int n_blocks = n;
-        if (!d_tab) {
-            std::vector<int> tab, bc, bn;           // (tab: the series column, then the other two)
-            for (int c = 0; c < n;) {               // blocks never straddle a series
-                int e = c + 1;
-                while (e < n && e - c < cpb && series_of_cell[(size_t)e] == series_of_cell[(size_t)c]) e++;
-                tab.push_back(series_of_cell[(size_t)c]);
-                bc.push_back(c);
-                bn.push_back(e - c);
-                c = e;
-            }
-            n_blocks = (int)tab.size();
-            if (n_blocks > L.max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow (fit)");
-            tab.insert(tab.end(), bc.begin(), bc.end());
-            tab.insert(tab.end(), bn.begin(), bn.end());
-            int *d_ws_tab = (int *)(ws + L.blk);
-            int rc = stage_h2d_async(device, stream, d_ws_tab, tab.data(), sizeof(int) * tab.size());
-            if (rc) return rc;
-            d_tab = d_ws_tab;
+// one-thread-per-cell kernel.  mode: 0 smoother, 1 propagate (serial kernel only).
+// It comes in two parts, so that a caller that runs the same cells again and again (the GA's fitness
+// pass) pays the host work once: smoother_tables uploads what depends on the cell -> series map alone,
+// smoother_enqueue launches and touches no host memory.
+struct SmootherTables {
+    bool scan = false;              // the scan kernel's FIT form runs
+    const int *d_tab = nullptr;     // its block table [3][n_blocks] on the device
+    int n_blocks = 0;
+};
+
+static bool smoother_is_scan(int T, int PP, int QQ, const WsLayout &L, int mode) {
+    return mode == 0 && L.img_stride && em_scan_supported(T, PP, QQ);
+}
+
+// The scan launch's block table (series, first cell, cells; blocks never straddle a series) into the
+// workspace, or the serial kernel's cell -> series map into d_soc; both through the pinned staging ring.
+static int smoother_tables(int device, hipStream_t stream, int T, int PP, int QQ, char *ws, const WsLayout &L,
+                           int n, const std::vector<int> &series_of_cell, int mode, int *d_soc,
+                           SmootherTables *out, const std::vector<char> *skip_series = nullptr) {
+    out->scan = smoother_is_scan(T, PP, QQ, L, mode);
+    if (!out->scan) return stage_h2d_async(device, stream, d_soc, series_of_cell.data(), sizeof(int) * (size_t)n);
+    const int cpb = em_scan_cells_per_block(T, PP, QQ);
+    std::vector<int> tab, bc, bn;           // (tab: the series column, then the other two)
+    for (int c = 0; c < n;) {
+        if (skip_series && (*skip_series)[(size_t)series_of_cell[(size_t)c]]) {      // (the caller runs these cells itself)
+            c++;
+            continue;
         }
+        int e = c + 1;
+        while (e < n && e - c < cpb && series_of_cell[(size_t)e] == series_of_cell[(size_t)c]) e++;
+        tab.push_back(series_of_cell[(size_t)c]);
+        bc.push_back(c);
+        bn.push_back(e - c);
+        c = e;
+    }
+    out->n_blocks = (int)tab.size();
+    if (out->n_blocks > L.max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow (fit)");
+    if (out->n_blocks == 0) return LDSR_OK;
+    tab.insert(tab.end(), bc.begin(), bc.end());
+    tab.insert(tab.end(), bn.begin(), bn.end());
+    int *d_ws_tab = (int *)(ws + L.blk);
+    out->d_tab = d_ws_tab;
+    return stage_h2d_async(device, stream, d_ws_tab, tab.data(), sizeof(int) * tab.size());
+}
+
+static int smoother_enqueue(hipStream_t stream, int T, int p, int q, int PP, int QQ, bool has_u, bool has_v,
+                            int shared_uv, char *ws, const WsLayout &L, int n, const SmootherTables &tb,
+                            const double *d_theta, int stdlik, int mode, double lambda, double *d_X,
+                            double *d_Y, double *d_V, double *d_J, double *d_lik, double *d_pen,
+                            int *d_status, const int *d_soc, bool scalar_only) {
+    if (tb.scan) {
+        const int *d_tab = tb.d_tab;
+        const int n_blocks = tb.n_blocks;
+        if (n_blocks == 0) return LDSR_OK;
         EmParams prm;
         memset(&prm, 0, sizeof(prm));
         prm.T = T; prm.p = p; prm.q = q; prm.has_u = has_u; prm.has_v = has_v;
@@ -780,8 +804,6 @@ static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, 
         HIPCHK(launch_em_scan(prm, PP, QQ, n_blocks, false, true, stream));
         return LDSR_OK;
     }
-    int rc = stage_h2d_async(device, stream, d_soc, series_of_cell.data(), sizeof(int) * (size_t)n);
-    if (rc) return rc;
     SmoothParams sp;
     memset(&sp, 0, sizeof(sp));
     sp.T = T; sp.p = p; sp.q = q; sp.has_u = has_u; sp.has_v = has_v;
@@ -802,6 +824,27 @@ static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, 
     sp.scalar_only = scalar_only;
     HIPCHK(launch_smooth(sp, PP, QQ, stream));
     return LDSR_OK;
+}
+
+// Both parts for a one-off pass.  d_tab_prebuilt: a block table [3][n], one block per cell, that the
+// device filled itself (the restart grid's winners).
+static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, int PP, int QQ,
+                           bool has_u, bool has_v, int shared_uv, char *ws, const WsLayout &L,
+                           int n, const std::vector<int> &series_of_cell, const double *d_theta,
+                           int stdlik, int mode, double lambda, double *d_X, double *d_Y,
+                           double *d_V, double *d_J, double *d_lik, double *d_pen, int *d_status,
+                           int *d_soc, bool scalar_only, const int *d_tab_prebuilt = nullptr) {
+    SmootherTables tb;
+    if (d_tab_prebuilt && smoother_is_scan(T, PP, QQ, L, mode)) {
+        tb.scan = true;
+        tb.d_tab = d_tab_prebuilt;
+        tb.n_blocks = n;
+    } else {
+        const int rc = smoother_tables(device, stream, T, PP, QQ, ws, L, n, series_of_cell, mode, d_soc, &tb);
+        if (rc) return rc;
+    }
+    return smoother_enqueue(stream, T, p, q, PP, QQ, has_u, has_v, shared_uv, ws, L, n, tb, d_theta, stdlik,
+                            mode, lambda, d_X, d_Y, d_V, d_J, d_lik, d_pen, d_status, d_soc, scalar_only);
 }
 
 // ---- one contiguous slice of the cell grid on one device ---------------------------------------
@@ -1510,6 +1553,198 @@ extern "C" int ldsr_penalized_lik_batch(int device, int n_series, int T, int p, 
                                         double lambda, double *pl) {
     return run_fit_kernel(3, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta, 0,
                           nullptr, nullptr, nullptr, nullptr, pl, nullptr, nullptr, lambda);
+}
+
+// ---- LDS_GA: the island genetic algorithm (ga.hip) ------------------------------------------------
+// The series are uploaded and prepared once, the fitness launch's tables are built once; a generation
+// is then smoother_enqueue (scalar-only, reading the current population buffer) + launch_ga_breed, and
+// nothing in that loop touches host memory.  Generations go out LDSR_GA_CHUNK at a time; between chunks
+// the problems' states come back (a few bytes each) to see whether every problem has stopped.
+extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                             const double *v, int shared_uv, const double *lb, const double *ub, double lambda,
+                             int num_islands, int pop_per_island, int maxiter, int run,
+                             unsigned long long seed, const double *suggestions, int n_suggestions,
+                             double *theta_best, double *pl_best, int *n_gen, double *trace,
+                             double *population, double *fitness) {
+    const int K = num_islands, n = pop_per_island;
+    if (K < 1) return fail(LDSR_EINVAL, "num_islands must be >= 1");
+    if (n < 2 || n > LDSR_GA_MAX_POP) return fail(LDSR_EINVAL, "pop_per_island must be in 2 .. 1024");
+    if (maxiter < 1) return fail(LDSR_EINVAL, "maxiter must be >= 1");
+    if (run < 1) return fail(LDSR_EINVAL, "run must be >= 1");
+    if (n_series < 1 || n_series > 65535) return fail(LDSR_EINVAL, "n_series must be in 1 .. 65535");
+    if ((long long)n_series * K * n > (long long)std::numeric_limits<int>::max() / 64)
+        return fail(LDSR_EINVAL, "n_series * num_islands * pop_per_island is too large");
+    std::vector<int> off((size_t)n_series + 1);
+    for (int s = 0; s <= n_series; s++) off[(size_t)s] = s * K * n;
+    int rc = check_common(n_series, T, p, q, y, off.data());
+    if (rc) return rc;
+    const int P = 6 + p + q;
+    if (!lb || !ub) return fail(LDSR_EINVAL, "lb and ub must not be NULL");
+    for (int c = 0; c < P; c++) {
+        if (!std::isfinite(lb[c]) || !std::isfinite(ub[c]) || !std::isfinite(ub[c] - lb[c]))
+            return fail(LDSR_EINVAL, "lb and ub must be finite");
+        if (lb[c] > ub[c]) return fail(LDSR_EINVAL, "lb must be <= ub in every gene");
+    }
+    if (!std::isfinite(lambda)) return fail(LDSR_EINVAL, "lambda must be finite");
+    if (n_suggestions < 0 || n_suggestions > n)
+        return fail(LDSR_EINVAL, "n_suggestions must be in 0 .. pop_per_island");
+    if (n_suggestions > 0 && !suggestions) return fail(LDSR_EINVAL, "suggestions must not be NULL");
+    if (!theta_best || !pl_best || !n_gen) return fail(LDSR_EINVAL, "theta_best, pl_best and n_gen must not be NULL");
+
+    const int n_cells = n_series * K * n;
+    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
+    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
+    IntrScope intr_scope;
+    ArenaLease lease;
+    rc = arena_acquire(device, &lease.a);
+    if (rc) return rc;
+    Arena *A = lease.a;
+    const WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_cells, LDSR_ALGO_SCAN, 1);
+    // The scan kernel whitens the inputs by Svv / Tuu and has no answer for a series where one of them is
+    // singular (fewer observations than columns of v, say), but Kalman_smoother does not need them: the
+    // cells of such a series take the serial smoother, whatever else shares the call.  series_prep finds
+    // those series, so the strip they need is known only after it: one more pass in that rare case.
+    const bool all_serial = !smoother_is_scan(T, PP, QQ, L, 0);
+    const size_t cells_per_problem = (size_t)K * n;
+    std::vector<char> singular((size_t)n_series, 0);
+    int n_sing = 0;
+    size_t o_y = 0, o_u = 0, o_v = 0, o_lb = 0, o_ub = 0, o_sg = 0, in_bytes = 0, o_st = 0, o_bt = 0, o_tr = 0,
+           out_bytes = 0, o_pop0 = 0, o_pop1 = 0, o_fit = 0, o_lik = 0, o_cst = 0, o_soc = 0, o_X = 0, o_V = 0, o_ws = 0;
+    const size_t pop_bytes = sizeof(double) * (size_t)n_cells * P;
+    char *dev = nullptr, *pin = nullptr, *ws = nullptr;
+    for (int pass = 0;; pass++) {
+        const size_t strip_cells = all_serial ? (size_t)n_cells : (size_t)n_sing * cells_per_problem;
+        Carver c;
+        o_y = c.take(sizeof(double) * (size_t)n_series * T);
+        o_u = c.take(u ? sizeof(double) * nuv * T * p : 0);
+        o_v = c.take(v ? sizeof(double) * nuv * T * q : 0);
+        o_lb = c.take(sizeof(double) * (size_t)P);
+        o_ub = c.take(sizeof(double) * (size_t)P);
+        o_sg = c.take(sizeof(double) * (size_t)n_series * n_suggestions * P);
+        in_bytes = c.o;
+        o_st = c.take(sizeof(GaState) * 2 * (size_t)n_series);      // both parities
+        o_bt = c.take(sizeof(double) * (size_t)n_series * P);
+        o_tr = c.take(sizeof(double) * (size_t)n_series * maxiter);
+        out_bytes = c.o - o_st;
+        o_pop0 = c.take(pop_bytes);
+        o_pop1 = c.take(pop_bytes);
+        o_fit = c.take(sizeof(double) * (size_t)n_cells);
+        o_lik = c.take(sizeof(double) * (size_t)n_cells);
+        o_cst = c.take(sizeof(int) * (size_t)n_cells);
+        o_soc = c.take(sizeof(int) * (size_t)n_cells);
+        o_X = c.take(sizeof(double) * strip_cells * T);
+        o_V = c.take(sizeof(double) * strip_cells * T);
+        o_ws = c.take(L.total);
+        const size_t sc_bytes = align256(2 * sizeof(int) * (size_t)n_series);      // (n_obs, status) of every series
+        rc = arena_reserve(A, c.o, in_bytes + align256(out_bytes) + sc_bytes);
+        if (rc) return rc;
+        dev = A->dev; pin = A->pin;
+        memcpy(pin + o_y, y, sizeof(double) * (size_t)n_series * T);
+        if (u) memcpy(pin + o_u, u, sizeof(double) * nuv * T * p);
+        if (v) memcpy(pin + o_v, v, sizeof(double) * nuv * T * q);
+        memcpy(pin + o_lb, lb, sizeof(double) * (size_t)P);
+        memcpy(pin + o_ub, ub, sizeof(double) * (size_t)P);
+        if (n_suggestions) memcpy(pin + o_sg, suggestions, sizeof(double) * (size_t)n_series * n_suggestions * P);
+        HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
+        ws = dev + o_ws;
+        HIPCHK(launch_series_prep(prep_params(n_series, T, p, q, PP, QQ, (const double *)(dev + o_y),
+                                              u ? (const double *)(dev + o_u) : nullptr,
+                                              v ? (const double *)(dev + o_v) : nullptr, shared_uv, ws, L, true),
+                                  n_series, A->stream));
+        if (all_serial || pass == 1) break;
+        static_assert(offsetof(SeriesConst, status) == sizeof(int), "the copy below takes n_obs and status");
+        int *h_sc = (int *)(pin + in_bytes + align256(out_bytes));
+        HIPCHK(hipMemcpy2DAsync(h_sc, 2 * sizeof(int), ws + L.sc, sizeof(SeriesConst), 2 * sizeof(int),
+                                (size_t)n_series, hipMemcpyDeviceToHost, A->stream));
+        HIPCHK(wait_stream(A->stream));
+        for (int s = 0; s < n_series; s++)
+            if (h_sc[2 * s + 1] != 0) { singular[(size_t)s] = 1; n_sing++; }
+        if (n_sing == 0) break;
+    }
+    std::vector<int> soc((size_t)n_cells);
+    for (int cc = 0; cc < n_cells; cc++) soc[(size_t)cc] = cc / (K * n);
+    SmootherTables tb;
+    rc = smoother_tables(device, A->stream, T, PP, QQ, ws, L, n_cells, soc, 0, (int *)(dev + o_soc), &tb, &singular);
+    if (rc) return rc;
+    if (n_sing) {       // (the serial smoother's cell -> series map, which the scan launch's table replaces)
+        rc = stage_h2d_async(device, A->stream, dev + o_soc, soc.data(), sizeof(int) * (size_t)n_cells);
+        if (rc) return rc;
+    }
+    SmootherTables tb_serial;       // (scan = false)
+    // one generation's fitness: the scan launch (or the serial one) over all cells, then the singular series
+    auto enqueue_fitness = [&](const double *d_pop) -> int {
+        int r = smoother_enqueue(A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv, ws, L,
+                                 n_cells, tb, d_pop, 0, 0, lambda, (double *)(dev + o_X), (double *)(dev + o_X),
+                                 (double *)(dev + o_V), (double *)(dev + o_V), (double *)(dev + o_lik),
+                                 (double *)(dev + o_fit), (int *)(dev + o_cst), (const int *)(dev + o_soc), true);
+        for (int s = 0, j = 0; s < n_series && !r && n_sing; s++) {
+            if (!singular[(size_t)s]) continue;
+            const size_t c0 = (size_t)s * cells_per_problem;
+            double *X = (double *)(dev + o_X) + (size_t)j * cells_per_problem * T;
+            double *V = (double *)(dev + o_V) + (size_t)j * cells_per_problem * T;
+            r = smoother_enqueue(A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv, ws, L,
+                                 (int)cells_per_problem, tb_serial, d_pop + c0 * P, 0, 0, lambda, X, X, V, V,
+                                 (double *)(dev + o_lik) + c0, (double *)(dev + o_fit) + c0,
+                                 (int *)(dev + o_cst) + c0, (const int *)(dev + o_soc) + c0, true);
+            j++;
+        }
+        return r;
+    };
+
+    GaParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.n_series = n_series; gp.K = K; gp.n = n; gp.P = P;
+    gp.maxiter = maxiter; gp.run = run;
+    gp.n_elite = std::max(1, (LDSR_GA_ELITE_PCT * n + 50) / 100);
+    gp.n_migr = std::max(1, LDSR_GA_MIGRATION_PCT * n / 100);
+    gp.migration_interval = LDSR_GA_MIGRATION_INTERVAL;
+    gp.n_sugg = n_suggestions;
+    gp.pcrossover = LDSR_GA_PCROSSOVER;
+    gp.pmutation = LDSR_GA_PMUTATION;
+    gp.seed = seed;
+    gp.lb = (const double *)(dev + o_lb);
+    gp.ub = (const double *)(dev + o_ub);
+    gp.sugg = n_suggestions ? (const double *)(dev + o_sg) : nullptr;
+    gp.pop[0] = (double *)(dev + o_pop0);
+    gp.pop[1] = (double *)(dev + o_pop1);
+    gp.fit = (const double *)(dev + o_fit);
+    gp.state[0] = (GaState *)(dev + o_st);
+    gp.state[1] = gp.state[0] + n_series;
+    gp.best_theta = (double *)(dev + o_bt);
+    gp.trace = (double *)(dev + o_tr);
+    HIPCHK(launch_ga_init(gp, A->stream));
+
+    char *pout = pin + in_bytes;
+    const GaState *h_state = (const GaState *)pout;
+    int g = 0;
+    for (bool all_done = false; !all_done;) {
+        const int g_end = (int)std::min((long long)maxiter, (long long)g + LDSR_GA_CHUNK);
+        for (; g < g_end; g++) {
+            rc = enqueue_fitness(gp.pop[g & 1]);
+            if (rc) return rc;
+            gp.g = g;
+            HIPCHK(launch_ga_breed(gp, A->stream));
+        }
+        HIPCHK(hipMemcpyAsync(pout, dev + o_st, out_bytes, hipMemcpyDeviceToHost, A->stream));
+        HIPCHK(wait_stream(A->stream));
+        intr_poll();
+        if (intr_raised()) return fail(LDSR_EINTERRUPTED, "interrupted by the caller's interrupt callback");
+        all_done = true;
+        for (int s = 0; s < n_series; s++)
+            if (!h_state[(size_t)(g & 1) * n_series + s].done) all_done = false;
+    }
+    // every problem is done: both population buffers hold its last evaluated generation, and the
+    // fitness buffer that generation's values
+    for (int s = 0; s < n_series; s++) {
+        const GaState &st = h_state[(size_t)(g & 1) * n_series + s];
+        pl_best[s] = st.best;
+        n_gen[s] = st.n_gen;
+    }
+    memcpy(theta_best, pout + (o_bt - o_st), sizeof(double) * (size_t)n_series * P);
+    if (trace) memcpy(trace, pout + (o_tr - o_st), sizeof(double) * (size_t)n_series * maxiter);
+    if (population) HIPCHK(hipMemcpy(population, gp.pop[g & 1], pop_bytes, hipMemcpyDeviceToHost));
+    if (fitness) HIPCHK(hipMemcpy(fitness, dev + o_fit, sizeof(double) * (size_t)n_cells, hipMemcpyDeviceToHost));
+    return LDSR_OK;
 }
 
 extern "C" int ldsr_propagate_batch(int device, int n_series, int T, int p, int q, const double *y,
