@@ -1,0 +1,40 @@
+"""LDS_BFGS on the Nakhon Phanom data (the reference's bundled NPannual / NPpc, T = 813): 100 restarts of
+the bound-constrained L-BFGS over ssqTrain on the GPU, both arms of the reference's call_method -- "BFGS"
+(fit = propagate) and "BFGS_smooth" (fit = Kalman_smoother) -- under the reference's selection rule
+(which.max of the minimised values, R/LDS_GA.R:174) and under the smallest value.
+usage: python examples/bfgs_reconstruction.py"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ldsr_amd  # noqa: E402
+
+
+def main():
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_data.json")))
+    qa, years = np.array(ref["NPannual"]["Qa"]), np.array(ref["NPannual"]["year"])
+    u = np.ascontiguousarray(np.array(ref["NPpc"]["data"]))          # 3 x 813, years 1200..2012
+    obs = np.log(qa)
+    y = np.full(u.shape[1], np.nan)
+    y[years[0] - 1200:years[0] - 1200 + len(obs)] = obs - obs.mean()
+    p = q = 3
+    lb = np.concatenate([[0.0], np.full(p, -1.0), [0.0], np.full(q, -1.0), [0.0, 0.0, -1.0, 0.0]])
+    ub = np.concatenate([[1.0], np.full(p, 1.0), [1.0], np.full(q, 1.0), [1.0, 1.0, 1.0, 1.0]])
+
+    for select in ("reference", "min"):
+        for smooth in (False, True):
+            m = ldsr_amd.LDS_BFGS(y, u, u, ub=ub, lb=lb, num_restarts=100, r_seed=1, select=select, smooth=smooth)
+            a = m["all"]
+            print("select = %-9s %-11s restart %3d of 100: ssq %.6f  lik %.6f  (%d iterations, %d evaluations; "
+                  "all restarts: ssq %.4f .. %.4f)" % (
+                      select, "BFGS_smooth" if smooth else "BFGS", a["selected"], m["pl"], m["lik"],
+                      a["n_iter"][a["selected"]], a["n_eval"][a["selected"]], np.nanmin(a["value"]), np.nanmax(a["value"])))
+
+
+if __name__ == "__main__":
+    main()

@@ -29,6 +29,13 @@
  *                            or the folds of cvLDS(method = "GA") in ONE call; the population never
  *                            leaves HBM.  An island GA of GA::gaisl's family by this project's own
  *                            specification, NOT gaisl's random stream
+ *   ldsr_bfgs_batch          LDS_BFGS (R/LDS_GA.R:155-184) and the BFGS / BFGS_smooth arms of call_method
+ *                            (R/LDS_reconstruction.R:70-86): every restart's whole bound-constrained
+ *                            L-BFGS run over ssqTrain inside one kernel launch, the selection of
+ *                            R/LDS_GA.R:174 and the winner's propagate / Kalman_smoother fit in ONE call.
+ *                            This project's own L-BFGS, NOT the iterates of the
+ *                            L-BFGS-B code behind stats::optim
+ *   ldsr_ssq_grad_batch      ssqTrain (R/LDS_GA.R:143-147) and its exact gradient for a batch of thetas
  *   ldsr_select_restart      the argmax-with-C>0 rule of R/LDS_reconstruction.R:50-58
  *   ldsr_simulate_batch      LDS_rep / one_LDS_rep (R/stochastics.R:18-63): num_reps stochastic
  *                            replicates of each of n_models thetas in one launch; with the uniforms
@@ -278,6 +285,50 @@ int ldsr_ga_batch(int device, int n_series, int T, int p, int q, const double *y
                   int num_islands, int pop_per_island, int maxiter, int run, unsigned long long seed,
                   const double *suggestions, int n_suggestions, double *theta_best, double *pl_best,
                   int *n_gen, double *trace, double *population, double *fitness);
+
+/* ssqTrain of R/LDS_GA.R:143-147 and its gradient: for every theta, with propagate's recursion
+ *   x_1 = mu1, x_{t+1} = A x_t + B u_t, Y_t = C x_t + D v_t  (src/EM.cpp:295-356, no measurement update),
+ *   ssq = sum over the observed y_t of (y_t - Y_t)^2   (NaN and +-Inf in y: missing),
+ * and grad = d ssq / d theta by the adjoint recursion: exact, one forward and one
+ * backward pass over the series.  The Q, R, V1 slots and the slots of an absent input have gradient 0.
+ *   ssq [n_cells]   grad [n_cells][6+p+q], may be NULL (values only).  Host pointers. */
+int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                        const double *v, int shared_uv, const int *cell_offsets, const double *theta,
+                        double *ssq, double *grad);
+
+/* LDS_BFGS (R/LDS_GA.R:155-184): a bound-constrained L-BFGS from every start point par0[c] that minimises
+ * ssq over the box [lb, ub], one persistent wavefront per (series, restart) cell: iterates, gradients and
+ * the curvature pairs never leave the wave, the whole run of a cell is one kernel launch.  The optimiser
+ * -- active set, two-loop direction, projected backtracking, stop rules -- is specified in INTEGRATION.md
+ * ("The bound-constrained L-BFGS"); it is NOT the L-BFGS-B code that stats::optim calls and does not
+ * reproduce its iterates.
+ *   par0    [n_cells][6+p+q] start points (projected into the box)     lb, ub [6+p+q] finite, lb <= ub
+ *   maxit   iterations at most (>= 1; optim: 100)      lmm   curvature pairs kept, 1 .. 8 (optim: 5)
+ *   factr   stop when (f_k - f_k+1) / max(|f_k|, |f_k+1|, 1) <= factr * 2^-52 (>= 0; optim: 1e7)
+ *   pgtol   stop when the projected gradient's largest entry is <= pgtol (>= 0; optim: 0)
+ *   select_max != 0: each series' winner is the restart with the LARGEST minimised value, the reference's
+ *           literal which.max(optim.vals) (R/LDS_GA.R:174); 0: the smallest.  NaN ignored, first index on
+ *           ties, -1 when no restart of the series has a finite value
+ *   fit_mode 0: the winner's fit is propagate(theta_w) (method = "BFGS"; J untouched), 1: Kalman_smoother
+ *           (theta_w) (method = "BFGS_smooth"); lik_w is that fit's standardised likelihood
+ *   par_all [n_cells][6+p+q], value_all, n_iter_all, n_eval_all (forward passes), status_all [n_cells]:
+ *           each may be NULL
+ *   winner [n_series] global cell index, theta_w [n_series][6+p+q], value_w [n_series]: required;
+ *   lik_w [n_series], X, Y, V, J [n_series][T]: each may be NULL.  Rows without a winner are NaN.
+ * Host pointers; only the winners' rows cross PCIe.  The interrupt callback is polled while the call waits,
+ * and the kernel looks at its flag every 8 iterations (LDSR_EINTERRUPTED).  One problem of the reference's
+ * default size is 100 cells and cannot fill the device: batch the folds of cvLDS into one call. */
+#define LDSR_BFGS_CONVERGED 0    /* a stop rule fired */
+#define LDSR_BFGS_MAXIT 1        /* maxit iterations ran */
+#define LDSR_BFGS_LINESEARCH 2   /* no acceptable step in 20 halvings: the cell keeps its best point */
+#define LDSR_BFGS_NONFINITE 3    /* f is not finite at the start: value NaN, par = par0 */
+#define LDSR_BFGS_INTERRUPTED 4  /* stopped by the interrupt callback (the call returns LDSR_EINTERRUPTED) */
+int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                    const double *v, int shared_uv, const int *cell_offsets, const double *par0,
+                    const double *lb, const double *ub, int maxit, int lmm, double factr, double pgtol,
+                    int select_max, int fit_mode, double *par_all, double *value_all, int *n_iter_all,
+                    int *n_eval_all, int *status_all, int *winner, double *theta_w, double *value_w,
+                    double *lik_w, double *X, double *Y, double *V, double *J);
 
 /* Stochastic replicates: one_LDS_rep / LDS_rep (R/stochastics.R:18-63) for n_models thetas x
  * num_reps replicates of T steps,

@@ -55,6 +55,11 @@ SIGNATURES = {
     "ldsr_ga_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp,
                                 C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, C.c_int,
                                 _dp, _dp, _ip, _dp, _dp, _dp]),
+    "ldsr_ssq_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _ip,
+                                      _dp, _dp, _dp]),
+    "ldsr_bfgs_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _ip, _dp,
+                                  _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                  _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ldsr_simulate_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp,
                                       _dp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, _dp, _dp, _dp]),
     "ldsr_simulate_draw_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int,

@@ -1,0 +1,135 @@
+"""LDS_BFGS of the reference (R/LDS_GA.R:155-184): learn theta by a bound-constrained L-BFGS that
+minimises ssqTrain from num_restarts random start points -- the BFGS and BFGS_smooth arms of
+call_method (R/LDS_reconstruction.R:70-86).
+
+Everything numeric runs on the GPU behind one library call (ldsr_bfgs_batch, include/ldsr_hip.h): one
+persistent wavefront per restart runs the whole optimisation, the winner is picked on the device and only
+its model crosses PCIe.  The optimiser is this project's own specification ("The
+bound-constrained L-BFGS"); it does not reproduce the iterates of the L-BFGS-B code behind stats::optim.
+This module only marshals and draws the start points -- there is no host implementation of the objective
+or of the optimiser."""
+import numpy as np
+
+from . import _lib
+from .api import _d, _dims, _i, _series, unpack_theta
+
+CONVERGED, MAXIT, LINESEARCH, NONFINITE, INTERRUPTED = 0, 1, 2, 3, 4
+_START_STREAM = 1 << 40       # counter-mode stream of restart r: _START_STREAM + r
+
+
+def _offsets(cell_offsets, S, n):
+    if cell_offsets is None:
+        if S != 1:
+            raise ValueError("cell_offsets is required with several series")
+        cell_offsets = [0, n]
+    off = np.ascontiguousarray(cell_offsets, dtype=np.int32)
+    if off.size != S + 1 or off[-1] != n:
+        raise ValueError("cell_offsets must have S+1 entries ending at n_cells")
+    return off
+
+
+def ssq_train(y, u, v, theta_packed, cell_offsets=None, grad=False, device=0):
+    """ssqTrain (R/LDS_GA.R:143-147) for a batch of packed thetas [n, 6+p+q]: the sum over the observed
+    y_t of (y_t - propagate(theta)$Y_t)^2.  With grad=True -> (ssq [n], gradient [n, 6+p+q])."""
+    Y, U, V, S, T, p, q, shared = _series(y, u, v)
+    theta = np.ascontiguousarray(np.atleast_2d(theta_packed), dtype=np.float64)
+    if theta.shape[1] != 6 + p + q:
+        raise ValueError("theta must be [n, %d]" % (6 + p + q))
+    n = theta.shape[0]
+    off = _offsets(cell_offsets, S, n)
+    f = np.empty(n)
+    g = np.empty_like(theta) if grad else None
+    _lib.check(_lib.lib().ldsr_ssq_grad_batch(device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off),
+                                              _d(theta), _d(f), _d(g)))
+    return (f, g) if grad else f
+
+
+def bfgs_batch(y, u, v, par0, lb, ub, cell_offsets=None, maxit=100, lmm=5, factr=1e7, pgtol=0.0,
+               select="reference", smooth=False, device=0, return_all=True):
+    """One L-BFGS run per row of par0 [n_cells, 6+p+q], all in one call.  y: [T], or [S, T] (the folds of
+    cvLDS with shared u, v) with cell_offsets [S+1].  select: "reference" is the reference's literal
+    which.max(optim.vals) (R/LDS_GA.R:174: the LARGEST of the minimised values), "min" the smallest.
+
+    Returns dict: winner [S] (global cell index, -1 = none), theta [S, P], value [S], lik [S],
+    X / Y / V [S, T] (J too with smooth=True: the fit is Kalman_smoother's, else propagate's); plus
+    "all" (per-cell par, value, n_iter, n_eval, status) when return_all."""
+    if select not in ("reference", "min"):
+        raise ValueError('select must be "reference" or "min"')
+    Y, U, V, S, T, p, q, shared = _series(y, u, v)
+    P = 6 + p + q
+    par0 = np.ascontiguousarray(np.atleast_2d(par0), dtype=np.float64)
+    if par0.shape[1] != P:
+        raise ValueError("par0 must be [n_cells, %d]" % P)
+    lb = np.ascontiguousarray(lb, dtype=np.float64).reshape(-1)
+    ub = np.ascontiguousarray(ub, dtype=np.float64).reshape(-1)
+    if lb.size != P or ub.size != P:
+        raise ValueError("lb and ub must have 6+p+q = %d entries" % P)
+    n = par0.shape[0]
+    off = _offsets(cell_offsets, S, n)
+    out = {"winner": np.empty(S, dtype=np.int32), "theta": np.empty((S, P)), "value": np.empty(S),
+           "lik": np.empty(S), "X": np.empty((S, T)), "Y": np.empty((S, T)), "V": np.empty((S, T))}
+    if smooth:
+        out["J"] = np.empty((S, T))
+    a = {}
+    if return_all:
+        a = {"par": np.empty((n, P)), "value": np.empty(n), "n_iter": np.empty(n, dtype=np.int32),
+             "n_eval": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.int32)}
+    _lib.check(_lib.lib().ldsr_bfgs_batch(
+        device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off), _d(par0), _d(lb), _d(ub), int(maxit),
+        int(lmm), float(factr), float(pgtol), int(select == "reference"), int(bool(smooth)),
+        _d(a.get("par")), _d(a.get("value")), _i(a.get("n_iter")), _i(a.get("n_eval")), _i(a.get("status")),
+        _i(out["winner"]), _d(out["theta"]), _d(out["value"]), _d(out["lik"]), _d(out["X"]), _d(out["Y"]),
+        _d(out["V"]), _d(out.get("J"))))
+    if return_all:
+        out["all"] = a
+    return out
+
+
+def start_points(lb, ub, num_restarts, seed=None, r_seed=None, first=0):
+    """[num_restarts, P] start points lb + (ub - lb) U.  r_seed=k: the draws of R's
+    `set.seed(k); replicate(num.restarts, runif(P, lb, ub))` (ldsr_amd/rrng.py; a coordinate with
+    lb == ub takes no uniform, as R's runif returns a without drawing when a == b).  Otherwise restart r
+    draws from counter-mode stream `first + r` of synth.py, so a restart's start point does not depend on
+    how many others share the call."""
+    lb = np.asarray(lb, dtype=np.float64).reshape(-1)
+    ub = np.asarray(ub, dtype=np.float64).reshape(-1)
+    n, P = int(num_restarts), lb.size
+    out = np.tile(lb, (n, 1))
+    if r_seed is not None:
+        from .rrng import RUniform
+        free = lb != ub
+        nf = int(free.sum())
+        if nf:
+            U = RUniform(r_seed).unif_rand(n * nf).reshape(n, nf)
+            out[:, free] = lb[free] + (ub[free] - lb[free]) * U
+        return out
+    from .synth import uniform
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1)[0])
+    for r in range(n):
+        out[r] = lb + (ub - lb) * uniform(seed, _START_STREAM + first + r, P)
+    return out
+
+
+def LDS_BFGS(y, u, v, ub=None, lb=None, num_restarts=100, seed=None, r_seed=None, select="reference",
+             smooth=False, maxit=100, device=0):
+    """-> {"theta", "fit", "lik", "pl", "all"}   (R/LDS_GA.R:176-183): theta as the reference's list, fit =
+    propagate(theta, u, v, y) with the standardised likelihood (smooth=True: Kalman_smoother(y, u, v,
+    theta), the BFGS_smooth arm, R/LDS_reconstruction.R:79-85), lik = fit's, pl = the selected restart's
+    minimised ssq; "all" = the per-restart par / value / n_iter / n_eval / status (+ selected, par0)."""
+    if ub is None or lb is None:
+        raise ValueError("LDS_BFGS needs ub and lb")     # R/LDS_reconstruction.R:176
+    p, q = _dims(u, v)
+    par0 = start_points(lb, ub, num_restarts, seed=seed, r_seed=r_seed)
+    r = bfgs_batch(y, u, v, par0, lb, ub, maxit=maxit, select=select, smooth=smooth, device=device)
+    if r["theta"].shape[0] != 1:
+        raise ValueError("LDS_BFGS takes one series; bfgs_batch runs several")
+    k = int(r["winner"][0])
+    if k < 0:
+        raise _lib.LdsrError("LDS_BFGS: no restart has a finite objective value")
+    fit = {"X": r["X"][0:1].copy(), "Y": r["Y"][0:1].copy(), "V": r["V"][0:1].copy()}
+    if smooth:
+        fit["J"] = r["J"][0:1].copy()
+    fit["lik"] = float(r["lik"][0])
+    return {"theta": unpack_theta(r["theta"][0], p, q), "fit": fit, "lik": fit["lik"], "pl": float(r["value"][0]),
+            "all": dict(r["all"], selected=k, par0=par0)}

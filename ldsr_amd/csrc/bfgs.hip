@@ -1,0 +1,395 @@
+// bfgs.hip -- the L-BFGS learner on the device (LDS_BFGS, the reference's R/LDS_GA.R:155-184; the
+// optimiser is this project's own specification, INTEGRATION.md "The bound-constrained L-BFGS").
+//
+// The objective is ssqTrain (R/LDS_GA.R:143-147) over propagate (src/EM.cpp:295-356):
+//     x_1 = mu1,  x_{t+1} = A x_t + B u_t,  Y_t = C x_t + D v_t,  r_t = y_t - Y_t (0 where y_t is not
+//     finite),  f = sum r_t^2,
+// and its exact gradient comes from the adjoint recursion lam_t = -2 C r_t + A lam_{t+1} (lam_{T+1} = 0):
+//     df/dC = -2 sum r_t x_t, df/dD_k = -2 sum r_t v_tk, df/dmu1 = lam_1,
+//     df/dA = sum_{t<T} lam_{t+1} x_t, df/dB_k = sum_{t<T} lam_{t+1} u_tk, nothing for Q, R, V1.
+//
+// One wave per (series, restart) cell, one wave per workgroup: restarts stop after very different
+// numbers of iterations, and a lone wave gives its LDS back the moment it is done.  In the vector
+// algebra lane i owns variable i (P = 6 + p + q <= 38); the coefficients the time passes need come out
+// of those lanes by v_readlane and stay in scalar registers.  In the forward pass lane l owns step
+// 64 k + l of chunk k, and x over a chunk is the inclusive affine scan of ldsr_simulate_kernel (DPP row
+// shifts and broadcasts, one fma by a power of A per round).  The backward pass is the same scan run
+// from the other end: it walks the chunks downwards with the lanes mirrored (lane l owns step
+// 64 k + 63 - l), so lam_{t+1} is the lane below.  It needs x_t and r_t again: the forward pass leaves
+// them in the wave's strip, 2 T doubles of LDS (T <= BFGS_LDS_MAX_T) or of a device workspace.
+// The sums are wave reductions (the halving form of em_scan_impl.h).
+//
+// Every product-sum is an explicit fma and contraction is off, so the forward pass gives the same f
+// with and without the gradient.
+#include "bfgs.h"
+#include "em_scan_impl.h"     // dppz / dppd, readlane_d, wave_sum_n
+#include "../../include/ldsr_hip.h"
+
+#pragma clang fp contract(off)
+
+#define MAXPQ LDSR_MAXPQ
+
+// one wave's view of its cell
+struct SsqCell {
+    const double *y, *u, *v;      // the series' rows (u, v null: absent)
+    double *strip;                // [2 T]: x_t, then r_t
+    int T, p, q;
+};
+
+__device__ __forceinline__ SsqCell ssq_cell(const SsqSeries &S, int cell, double *lds_strip) {
+    const int s = S.series_of_cell[cell];
+    SsqCell c;
+    c.T = S.T; c.p = S.p; c.q = S.q;
+    c.y = S.y + (size_t)s * S.T;
+    c.u = S.u ? S.u + (size_t)s * S.u_stride : nullptr;
+    c.v = S.v ? S.v + (size_t)s * S.v_stride : nullptr;
+    c.strip = S.strip ? S.strip + (size_t)blockIdx.x * 2 * S.T : lds_strip;
+    return c;
+}
+
+// inclusive scan x_l = A x_{l-1} + e_l over the 64 lanes (ldsr_simulate_kernel's)
+struct AffineScan {
+    double A, A2, A4, A8, P16, P32;
+    __device__ __forceinline__ AffineScan(double A_, int lane) : A(A_) {
+        A2 = A * A; A4 = A2 * A2; A8 = A4 * A4;
+        const double A16 = A8 * A8;
+        P16 = A;
+        if (lane & 1) P16 *= A;
+        if (lane & 2) P16 *= A2;
+        if (lane & 4) P16 *= A4;
+        if (lane & 8) P16 *= A8;
+        P32 = (lane & 16) ? P16 * A16 : P16;
+    }
+    __device__ __forceinline__ double run(double x) const {
+        x = fma(A, dppz<DPP_ROW_SHR(1)>(x), x);
+        x = fma(A2, dppz<DPP_ROW_SHR(2)>(x), x);
+        x = fma(A4, dppz<DPP_ROW_SHR(4)>(x), x);
+        x = fma(A8, dppz<DPP_ROW_SHR(8)>(x), x);
+        x = fma(P16, dppd<DPP_ROW_BCAST15, 0xA>(0.0, x), x);    // lane 15 -> row 1, lane 47 -> row 3
+        x = fma(P32, dppd<DPP_ROW_BCAST31, 0xC>(0.0, x), x);    // lane 31 -> rows 2, 3
+        return x;
+    }
+};
+
+// f at the theta whose variable i sits in lane i (xv); with GRAD also the gradient, variable i in lane i
+// (0 in the lanes beyond P).  Both results are the same in every lane resp. wave-uniform.
+template <bool GRAD>
+__device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane, double *g_out) {
+    const int T = c.T, p = c.p, q = c.q;
+    const double A = readlane_d(xv, 0), C = readlane_d(xv, 1 + p), mu1 = readlane_d(xv, 4 + p + q);
+    double Bk[MAXPQ], Dk[MAXPQ];
+#pragma unroll
+    for (int k = 0; k < MAXPQ; k++) {
+        Bk[k] = (c.u && k < p) ? readlane_d(xv, 1 + k) : 0.0;
+        Dk[k] = (c.v && k < q) ? readlane_d(xv, 2 + p + k) : 0.0;
+    }
+    const AffineScan scan(A, lane);
+
+    double red[2 + MAXPQ];          // f, sum r x, sum r v_k
+#pragma unroll
+    for (int k = 0; k < 2 + MAXPQ; k++) red[k] = 0.0;
+    double carry = 0.0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool in = t < T;
+        double e = 0.0, dv = 0.0, yt = NAN;
+        double vt[MAXPQ];
+#pragma unroll
+        for (int k = 0; k < MAXPQ; k++) vt[k] = 0.0;
+        if (in) {
+            if (t == 0) {
+                e = mu1;
+            } else if (c.u) {
+                const double *ut = c.u + (size_t)(t - 1) * p;
+#pragma unroll
+                for (int k = 0; k < MAXPQ; k++)
+                    if (k < p) e = fma(Bk[k], ut[k], e);
+            }
+            if (c.v) {
+                const double *vr = c.v + (size_t)t * q;
+#pragma unroll
+                for (int k = 0; k < MAXPQ; k++)
+                    if (k < q) {
+                        vt[k] = vr[k];
+                        dv = fma(Dk[k], vt[k], dv);
+                    }
+            }
+            yt = c.y[t];
+        }
+        if (lane == 0) e = fma(A, carry, e);
+        double x = scan.run(e);
+        carry = readlane_d(x, 63);
+        const bool obs = in && isfinite(yt);
+        const double r = obs ? yt - fma(C, x, dv) : 0.0;
+        red[0] = fma(r, r, red[0]);
+        if (GRAD) {
+            if (in) {
+                c.strip[t] = x;
+                c.strip[T + t] = r;
+            }
+            if (obs) {
+                red[1] = fma(r, x, red[1]);
+#pragma unroll
+                for (int k = 0; k < MAXPQ; k++)
+                    if (k < q) red[2 + k] = fma(r, vt[k], red[2 + k]);
+            }
+        }
+    }
+    if (!GRAD) {
+        double f1[1] = {red[0]};
+        wave_sum_n<1>(f1);
+        return f1[0];
+    }
+    wave_sum_n<2 + MAXPQ>(red);
+    const double f = red[0];
+    double g = 0.0;
+    if (lane == 1 + p) g = -2.0 * red[1];
+    if (c.v) {
+#pragma unroll
+        for (int k = 0; k < MAXPQ; k++)
+            if (k < q && lane == 2 + p + k) g = -2.0 * red[2 + k];
+    }
+
+    // the strip is written by one lane and read by another
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+
+    double rb[1 + MAXPQ];           // sum lam_{t+1} x_t, sum lam_{t+1} u_tk
+#pragma unroll
+    for (int k = 0; k < 1 + MAXPQ; k++) rb[k] = 0.0;
+    const double m2C = -2.0 * C;
+    carry = 0.0;                    // lam_{T+1}
+    for (int t0 = ((T - 1) >> 6) << 6; t0 >= 0; t0 -= 64) {
+        const int t = t0 + 63 - lane;
+        const bool in = t < T;
+        double xt = 0.0, r = 0.0;
+        if (in) {
+            xt = c.strip[t];
+            r = c.strip[T + t];
+        }
+        double e = m2C * r;
+        if (lane == 0) e = fma(A, carry, e);
+        const double lam = scan.run(e);
+        const double lam_next = dppd<DPP_WAVE_SHR1, 0xF>(carry, lam);     // lam_{t+1}: the lane below, or the chunk above
+        carry = readlane_d(lam, 63);
+        if (t < T - 1) {
+            rb[0] = fma(lam_next, xt, rb[0]);
+            if (c.u) {
+                const double *ut = c.u + (size_t)t * p;
+#pragma unroll
+                for (int k = 0; k < MAXPQ; k++)
+                    if (k < p) rb[1 + k] = fma(lam_next, ut[k], rb[1 + k]);
+            }
+        }
+    }
+    wave_sum_n<1 + MAXPQ>(rb);
+    if (lane == 0) g = rb[0];
+    if (c.u) {
+#pragma unroll
+        for (int k = 0; k < MAXPQ; k++)
+            if (k < p && lane == 1 + k) g = rb[1 + k];
+    }
+    if (lane == 4 + p + q) g = carry;      // lam_1
+    // the next forward pass overwrites the strip other lanes have just read
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    *g_out = g;
+    return f;
+}
+
+__device__ __forceinline__ double wave_sum1(double x) {
+    double a[1] = {x};
+    wave_sum_n<1>(a);
+    return a[0];
+}
+
+__device__ __forceinline__ double wave_max1(double x) {      // x >= 0 or NaN; NaN in any lane gives NaN
+    bool bad = x != x;
+    for (int d = 32; d >= 1; d >>= 1) x = fmax(x, __shfl_xor(x, d, 64));
+    return __any(bad) ? NAN : x;
+}
+
+__global__ __launch_bounds__(64) void ldsr_ssq_grad_kernel(SsqParams prm) {
+    extern __shared__ double lds_strip[];
+    const int lane = threadIdx.x;
+    const int P = 6 + prm.S.p + prm.S.q;
+    for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
+        const SsqCell c = ssq_cell(prm.S, cell, lds_strip);
+        const double xv = lane < P ? prm.theta[(size_t)cell * P + lane] : 0.0;
+        double f, g = 0.0;
+        if (prm.grad) f = ssq_eval<true>(c, xv, lane, &g);
+        else f = ssq_eval<false>(c, xv, lane, nullptr);
+        if (lane == 0) prm.ssq[cell] = f;
+        if (prm.grad && lane < P) prm.grad[(size_t)cell * P + lane] = g;
+    }
+}
+
+// The optimiser: INTEGRATION.md "The bound-constrained L-BFGS", step for step.
+__global__ __launch_bounds__(64) void ldsr_bfgs_kernel(BfgsParams prm) {
+    extern __shared__ double lds_strip[];
+    const int lane = threadIdx.x;
+    const int P = 6 + prm.S.p + prm.S.q;
+    const bool mine = lane < P;
+    const double lo = mine ? prm.lb[lane] : 0.0, hi = mine ? prm.ub[lane] : 0.0;
+    for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
+        const SsqCell c = ssq_cell(prm.S, cell, lds_strip);
+        const double x_in = mine ? prm.par0[(size_t)cell * P + lane] : 0.0;
+        double x = fmin(fmax(x_in, lo), hi);
+        double g = 0.0;
+        double f = ssq_eval<true>(c, x, lane, &g);
+        int n_eval = 1, k = 0, status = LDSR_BFGS_MAXIT;
+        if (!isfinite(f)) {
+            if (mine) prm.par[(size_t)cell * P + lane] = x_in;
+            if (lane == 0) {
+                prm.value[cell] = NAN;
+                prm.n_iter[cell] = 0;
+                prm.n_eval[cell] = n_eval;
+                prm.status[cell] = LDSR_BFGS_NONFINITE;
+            }
+            continue;
+        }
+        double sh[BFGS_MAX_LMM], yh[BFGS_MAX_LMM];      // curvature pairs, newest first
+#pragma unroll
+        for (int j = 0; j < BFGS_MAX_LMM; j++) { sh[j] = 0.0; yh[j] = 0.0; }
+        int cnt = 0;
+        for (;;) {
+            // the active set and the projected gradient
+            const bool active = !mine || lo == hi || (x <= lo && g > 0.0) || (x >= hi && g < 0.0);
+            const double pg = active ? 0.0 : g;
+            const double pgn = wave_max1(fabs(pg));
+            if (pgn <= prm.pgtol) { status = LDSR_BFGS_CONVERGED; break; }
+            if (k >= prm.maxit) { status = LDSR_BFGS_MAXIT; break; }
+            if (prm.intr && (k & 7) == 0 && *(const volatile int *)prm.intr != 0) { status = LDSR_BFGS_INTERRUPTED; break; }
+
+            // the direction: two-loop recursion over the pairs restricted to the free variables
+            double d = -pg;
+            if (cnt > 0) {
+                double sy_yy[2 * BFGS_MAX_LMM];
+#pragma unroll
+                for (int j = 0; j < BFGS_MAX_LMM; j++) {
+                    const double sj = active ? 0.0 : sh[j], yj = active ? 0.0 : yh[j];
+                    sy_yy[2 * j] = sj * yj;
+                    sy_yy[2 * j + 1] = yj * yj;
+                }
+                wave_sum_n<2 * BFGS_MAX_LMM>(sy_yy);
+                double al[BFGS_MAX_LMM];
+                double qv = pg, gamma = 1.0;
+                bool have_gamma = false;
+#pragma unroll
+                for (int j = 0; j < BFGS_MAX_LMM; j++) {
+                    al[j] = 0.0;
+                    const double sy = sy_yy[2 * j], yy = sy_yy[2 * j + 1];
+                    if (j < cnt && sy > 2.2e-16 * yy) {
+                        al[j] = wave_sum1(active ? 0.0 : sh[j] * qv) / sy;
+                        if (!active) qv = fma(-al[j], yh[j], qv);
+                        if (!have_gamma) { gamma = sy / yy; have_gamma = true; }
+                    }
+                }
+                qv *= gamma;
+#pragma unroll
+                for (int j = BFGS_MAX_LMM - 1; j >= 0; j--) {
+                    const double sy = sy_yy[2 * j], yy = sy_yy[2 * j + 1];
+                    if (j < cnt && sy > 2.2e-16 * yy) {
+                        const double be = wave_sum1(active ? 0.0 : yh[j] * qv) / sy;
+                        if (!active) qv = fma(al[j] - be, sh[j], qv);
+                    }
+                }
+                d = active ? 0.0 : -qv;
+            }
+            double gd = wave_sum1(g * d);
+            if (cnt > 0 && !(gd < 0.0)) {       // not a descent direction: steepest descent, memory cleared
+                cnt = 0;
+                d = -pg;
+                gd = wave_sum1(g * d);
+            }
+
+            // projected backtracking
+            double alpha = k == 0 ? fmin(1.0, 1.0 / pgn) : 1.0;
+            double xt = x, ft = f;
+            bool ok = false;
+            for (int trial = 0; trial < BFGS_LS_TRIALS; trial++) {
+                xt = fmin(fmax(fma(alpha, d, x), lo), hi);
+                ft = ssq_eval<false>(c, xt, lane, nullptr);
+                n_eval++;
+                const double slope = wave_sum1(g * (xt - x));
+                if (isfinite(ft) && ft <= fma(1e-4, slope, f)) { ok = true; break; }
+                alpha *= 0.5;
+            }
+            if (!ok) { status = LDSR_BFGS_LINESEARCH; break; }
+
+            // the gradient at the accepted point, the new pair, the stop rule
+            double gt = 0.0;
+            ft = ssq_eval<true>(c, xt, lane, &gt);
+            n_eval++;
+            const double sv = xt - x, yv = gt - g;
+            double pr[2] = {sv * yv, yv * yv};
+            wave_sum_n<2>(pr);
+            if (pr[0] > 2.2e-16 * pr[1]) {
+#pragma unroll
+                for (int j = BFGS_MAX_LMM - 1; j > 0; j--) { sh[j] = sh[j - 1]; yh[j] = yh[j - 1]; }
+                sh[0] = sv;
+                yh[0] = yv;
+                cnt = min(cnt + 1, prm.lmm);
+            }
+            const double drop = (f - ft) / fmax(fmax(fabs(f), fabs(ft)), 1.0);
+            x = xt; f = ft; g = gt;
+            k++;
+            if (drop <= prm.ftol) { status = LDSR_BFGS_CONVERGED; break; }
+        }
+        if (mine) prm.par[(size_t)cell * P + lane] = x;
+        if (lane == 0) {
+            prm.value[cell] = f;
+            prm.n_iter[cell] = k;
+            prm.n_eval[cell] = n_eval;
+            prm.status[cell] = status;
+        }
+    }
+}
+
+// One wave per series: the first largest (select_max) or first smallest finite value of its cells.
+__global__ __launch_bounds__(64) void ldsr_bfgs_select_kernel(BfgsSelectParams prm) {
+    const int s = blockIdx.x, lane = threadIdx.x, P = prm.P;
+    const int c0 = prm.cell_offsets[s], c1 = prm.cell_offsets[s + 1];
+    double bv = 0.0;
+    int bi = -1;
+    for (int cc = c0 + lane; cc < c1; cc += 64) {
+        const double f = prm.value[cc];
+        if (isfinite(f) && (bi < 0 || (prm.select_max ? f > bv : f < bv))) { bv = f; bi = cc; }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(bv, d, 64);
+        const int oi = __shfl_xor(bi, d, 64);
+        if (oi >= 0 && (bi < 0 || (prm.select_max ? ov > bv : ov < bv) || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) {
+        prm.winner[s] = bi;
+        prm.value_w[s] = bi >= 0 ? bv : NAN;
+    }
+    if (lane < P) prm.theta_w[(size_t)s * P + lane] = bi >= 0 ? prm.par[(size_t)bi * P + lane] : NAN;
+}
+
+int bfgs_waves(int n_cells, int T) {
+    // in LDS mode the hardware hands out cells as waves retire; the workspace mode bounds its strip
+    return T <= BFGS_LDS_MAX_T ? n_cells : (n_cells < 2048 ? n_cells : 2048);
+}
+
+static size_t bfgs_lds_bytes(int T) { return T <= BFGS_LDS_MAX_T ? sizeof(double) * 2 * (size_t)T : 0; }
+
+hipError_t launch_ssq_grad(const SsqParams &prm, hipStream_t stream) {
+    if (prm.S.n_cells <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ldsr_ssq_grad_kernel, dim3((unsigned)bfgs_waves(prm.S.n_cells, prm.S.T)), dim3(64),
+                       prm.grad ? bfgs_lds_bytes(prm.S.T) : 0, stream, prm);
+    return hipGetLastError();
+}
+
+hipError_t launch_bfgs(const BfgsParams &prm, hipStream_t stream) {
+    if (prm.S.n_cells <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ldsr_bfgs_kernel, dim3((unsigned)bfgs_waves(prm.S.n_cells, prm.S.T)), dim3(64),
+                       bfgs_lds_bytes(prm.S.T), stream, prm);
+    return hipGetLastError();
+}
+
+hipError_t launch_bfgs_select(const BfgsSelectParams &prm, hipStream_t stream) {
+    hipLaunchKernelGGL(ldsr_bfgs_select_kernel, dim3((unsigned)prm.n_series), dim3(64), 0, stream, prm);
+    return hipGetLastError();
+}

@@ -21,6 +21,7 @@
 #include "ldsr_kernels.h"
 #include "em_pair_impl.h"      // (layout constants only)
 #include "ga.h"
+#include "bfgs.h"
 #include "source_hash.h"       // LDSR_SOURCE_HASH, written by the Makefile
 
 static thread_local std::string g_err;
@@ -1744,6 +1745,245 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
     if (trace) memcpy(trace, pout + (o_tr - o_st), sizeof(double) * (size_t)n_series * maxiter);
     if (population) HIPCHK(hipMemcpy(population, gp.pop[g & 1], pop_bytes, hipMemcpyDeviceToHost));
     if (fitness) HIPCHK(hipMemcpy(fitness, dev + o_fit, sizeof(double) * (size_t)n_cells, hipMemcpyDeviceToHost));
+    return LDSR_OK;
+}
+
+// ---- LDS_BFGS: ssqTrain, its gradient and the L-BFGS learner (bfgs.hip) ----------------------------
+// What both entries upload: the raw series (the kernels read the ABI's time-major u, v as they are and
+// find the missing y_t themselves), the cell -> series map and the cells' thetas.
+struct SsqUpload {
+    size_t o_y, o_u, o_v, o_soc, o_th;
+};
+static SsqUpload ssq_carve(Carver &c, int n_series, int T, int p, int q, const double *u, const double *v,
+                           int shared_uv, int n_cells) {
+    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
+    SsqUpload U;
+    U.o_y = c.take(sizeof(double) * (size_t)n_series * T);
+    U.o_u = c.take(u ? sizeof(double) * nuv * T * p : 0);
+    U.o_v = c.take(v ? sizeof(double) * nuv * T * q : 0);
+    U.o_soc = c.take(sizeof(int) * (size_t)n_cells);
+    U.o_th = c.take(sizeof(double) * (size_t)n_cells * (6 + p + q));
+    return U;
+}
+static void ssq_stage(const SsqUpload &U, char *pin, int n_series, int T, int p, int q, const double *y,
+                      const double *u, const double *v, int shared_uv, const int *cell_offsets,
+                      const double *theta) {
+    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
+    memcpy(pin + U.o_y, y, sizeof(double) * (size_t)n_series * T);
+    if (u) memcpy(pin + U.o_u, u, sizeof(double) * nuv * T * p);
+    if (v) memcpy(pin + U.o_v, v, sizeof(double) * nuv * T * q);
+    int *soc = (int *)(pin + U.o_soc);
+    for (int s = 0; s < n_series; s++)
+        for (int cc = cell_offsets[s]; cc < cell_offsets[s + 1]; cc++) soc[cc] = s;
+    memcpy(pin + U.o_th, theta, sizeof(double) * (size_t)cell_offsets[n_series] * (6 + p + q));
+}
+static SsqSeries ssq_series(const SsqUpload &U, char *dev, int T, int p, int q, const double *u, const double *v,
+                            int shared_uv, int n_cells, double *d_strip) {
+    SsqSeries S;
+    S.n_cells = n_cells; S.T = T; S.p = p; S.q = q;
+    S.y = (const double *)(dev + U.o_y);
+    S.u = u ? (const double *)(dev + U.o_u) : nullptr;
+    S.v = v ? (const double *)(dev + U.o_v) : nullptr;
+    S.u_stride = shared_uv ? 0 : (long)T * p;
+    S.v_stride = shared_uv ? 0 : (long)T * q;
+    S.series_of_cell = (const int *)(dev + U.o_soc);
+    S.strip = d_strip;
+    return S;
+}
+static size_t ssq_strip_bytes(int n_cells, int T) {
+    return T <= BFGS_LDS_MAX_T ? 0 : sizeof(double) * 2 * (size_t)T * (size_t)bfgs_waves(n_cells, T);
+}
+
+extern "C" int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q, const double *y,
+                                   const double *u, const double *v, int shared_uv, const int *cell_offsets,
+                                   const double *theta, double *ssq, double *grad) {
+    int rc = check_common(n_series, T, p, q, y, cell_offsets);
+    if (rc) return rc;
+    if (!theta || !ssq) return fail(LDSR_EINVAL, "theta and ssq must not be NULL");
+    const int n_cells = cell_offsets[n_series];
+    if (n_cells == 0) return LDSR_OK;
+    const int P = 6 + p + q;
+    ArenaLease lease;
+    rc = arena_acquire(device, &lease.a);
+    if (rc) return rc;
+    Arena *A = lease.a;
+    Carver c;
+    const SsqUpload U = ssq_carve(c, n_series, T, p, q, u, v, shared_uv, n_cells);
+    const size_t in_bytes = c.o;
+    const size_t o_f = c.take(sizeof(double) * (size_t)n_cells);
+    const size_t o_g = c.take(grad ? sizeof(double) * (size_t)n_cells * P : 0);
+    const size_t out_bytes = c.o - o_f;
+    const size_t strip_bytes = grad ? ssq_strip_bytes(n_cells, T) : 0;
+    const size_t o_strip = c.take(strip_bytes);
+    rc = arena_reserve(A, c.o, in_bytes + align256(out_bytes));
+    if (rc) return rc;
+    char *dev = A->dev, *pin = A->pin;
+    ssq_stage(U, pin, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta);
+    HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
+    SsqParams sp;
+    sp.S = ssq_series(U, dev, T, p, q, u, v, shared_uv, n_cells, strip_bytes ? (double *)(dev + o_strip) : nullptr);
+    sp.theta = (const double *)(dev + U.o_th);
+    sp.ssq = (double *)(dev + o_f);
+    sp.grad = grad ? (double *)(dev + o_g) : nullptr;
+    HIPCHK(launch_ssq_grad(sp, A->stream));
+    char *pout = pin + in_bytes;
+    HIPCHK(hipMemcpyAsync(pout, dev + o_f, out_bytes, hipMemcpyDeviceToHost, A->stream));
+    HIPCHK(hipStreamSynchronize(A->stream));
+    memcpy(ssq, pout, sizeof(double) * (size_t)n_cells);
+    if (grad) memcpy(grad, pout + (o_g - o_f), sizeof(double) * (size_t)n_cells * P);
+    return LDSR_OK;
+}
+
+// One launch runs every cell's optimisation from start to stop; a second picks the winners; the host then
+// sees winner / theta_w / value_w, and the winners' fit is one pass of the existing propagate / FIT
+// kernels on the prepared series.
+extern "C" int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                               const double *v, int shared_uv, const int *cell_offsets, const double *par0,
+                               const double *lb, const double *ub, int maxit, int lmm, double factr,
+                               double pgtol, int select_max, int fit_mode, double *par_all, double *value_all,
+                               int *n_iter_all, int *n_eval_all, int *status_all, int *winner, double *theta_w,
+                               double *value_w, double *lik_w, double *X, double *Y, double *V, double *J) {
+    int rc = check_common(n_series, T, p, q, y, cell_offsets);
+    if (rc) return rc;
+    const int P = 6 + p + q;
+    if (!lb || !ub) return fail(LDSR_EINVAL, "lb and ub must not be NULL");
+    for (int c = 0; c < P; c++) {
+        if (!std::isfinite(lb[c]) || !std::isfinite(ub[c]) || !std::isfinite(ub[c] - lb[c]))
+            return fail(LDSR_EINVAL, "lb and ub must be finite");
+        if (lb[c] > ub[c]) return fail(LDSR_EINVAL, "lb must be <= ub in every variable");
+    }
+    if (maxit < 1) return fail(LDSR_EINVAL, "maxit must be >= 1");
+    if (lmm < 1 || lmm > BFGS_MAX_LMM) return fail(LDSR_EINVAL, "lmm must be in 1 .. 8");
+    if (!(factr >= 0.0) || !std::isfinite(factr)) return fail(LDSR_EINVAL, "factr must be finite and >= 0");
+    if (!(pgtol >= 0.0) || !std::isfinite(pgtol)) return fail(LDSR_EINVAL, "pgtol must be finite and >= 0");
+    if (fit_mode != 0 && fit_mode != 1) return fail(LDSR_EINVAL, "fit_mode must be 0 (propagate) or 1 (Kalman_smoother)");
+    if (!par0) return fail(LDSR_EINVAL, "par0 must not be NULL");
+    if (!winner || !theta_w || !value_w) return fail(LDSR_EINVAL, "winner, theta_w and value_w must not be NULL");
+    const int n_cells = cell_offsets[n_series];
+    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
+    const bool want_fit = lik_w || X || Y || V || (J && fit_mode == 1);
+    IntrScope intr_scope;
+    ArenaLease lease;
+    rc = arena_acquire(device, &lease.a);
+    if (rc) return rc;
+    Arena *A = lease.a;
+    const WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_series, LDSR_ALGO_SCAN, 1);
+    const size_t nT = (size_t)n_series * T;
+    Carver c;
+    const SsqUpload U = ssq_carve(c, n_series, T, p, q, u, v, shared_uv, n_cells);
+    const size_t o_lb = c.take(sizeof(double) * (size_t)P);
+    const size_t o_ub = c.take(sizeof(double) * (size_t)P);
+    const size_t o_off = c.take(sizeof(int) * ((size_t)n_series + 1));
+    const size_t in_bytes = c.o;
+    // (what the host always reads, then the optional per-cell results, then the winners' fit)
+    const size_t o_win = c.take(sizeof(int) * (size_t)n_series);
+    const size_t o_thw = c.take(sizeof(double) * (size_t)n_series * P);
+    const size_t o_vw = c.take(sizeof(double) * (size_t)n_series);
+    const size_t sel_bytes = c.o - o_win;
+    const size_t o_par = c.take(sizeof(double) * (size_t)n_cells * P);
+    const size_t o_val = c.take(sizeof(double) * (size_t)n_cells);
+    const size_t o_nit = c.take(sizeof(int) * (size_t)n_cells);
+    const size_t o_nev = c.take(sizeof(int) * (size_t)n_cells);
+    const size_t o_st = c.take(sizeof(int) * (size_t)n_cells);
+    const size_t cell_bytes = c.o - o_par;
+    const size_t o_lik = c.take(sizeof(double) * (size_t)n_series);
+    const size_t o_X = c.take(sizeof(double) * nT);
+    const size_t o_Y = c.take(sizeof(double) * nT);
+    const size_t o_V = c.take(sizeof(double) * nT);
+    const size_t o_J = c.take(sizeof(double) * nT);
+    const size_t fit_bytes = c.o - o_lik;
+    const size_t o_fst = c.take(sizeof(int) * (size_t)n_series);
+    const size_t o_fsoc = c.take(sizeof(int) * (size_t)n_series);
+    const size_t o_fth = c.take(sizeof(double) * (size_t)n_series * P);
+    const size_t strip_bytes = ssq_strip_bytes(n_cells, T);
+    const size_t o_strip = c.take(strip_bytes);
+    const size_t o_ws = c.take(L.total);
+    const bool want_cells = par_all || value_all || n_iter_all || n_eval_all || status_all;
+    rc = arena_reserve(A, c.o, in_bytes + align256(sel_bytes) + align256(std::max(cell_bytes, fit_bytes)));
+    if (rc) return rc;
+    char *dev = A->dev, *pin = A->pin;
+    ssq_stage(U, pin, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, par0);
+    memcpy(pin + o_lb, lb, sizeof(double) * (size_t)P);
+    memcpy(pin + o_ub, ub, sizeof(double) * (size_t)P);
+    memcpy(pin + o_off, cell_offsets, sizeof(int) * ((size_t)n_series + 1));
+    HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
+
+    BfgsParams bp;
+    bp.S = ssq_series(U, dev, T, p, q, u, v, shared_uv, n_cells, strip_bytes ? (double *)(dev + o_strip) : nullptr);
+    bp.par0 = (const double *)(dev + U.o_th);
+    bp.lb = (const double *)(dev + o_lb);
+    bp.ub = (const double *)(dev + o_ub);
+    bp.maxit = maxit; bp.lmm = lmm;
+    bp.ftol = factr * 0x1p-52; bp.pgtol = pgtol;
+    bp.intr = intr_flag_for_kernels();
+    bp.par = (double *)(dev + o_par);
+    bp.value = (double *)(dev + o_val);
+    bp.n_iter = (int *)(dev + o_nit);
+    bp.n_eval = (int *)(dev + o_nev);
+    bp.status = (int *)(dev + o_st);
+    HIPCHK(launch_bfgs(bp, A->stream));
+    BfgsSelectParams sl;
+    sl.n_series = n_series; sl.P = P; sl.select_max = select_max;
+    sl.cell_offsets = (const int *)(dev + o_off);
+    sl.par = bp.par; sl.value = bp.value;
+    sl.winner = (int *)(dev + o_win);
+    sl.theta_w = (double *)(dev + o_thw);
+    sl.value_w = (double *)(dev + o_vw);
+    HIPCHK(launch_bfgs_select(sl, A->stream));
+    char *psel = pin + in_bytes, *pbig = psel + align256(sel_bytes);
+    HIPCHK(hipMemcpyAsync(psel, dev + o_win, sel_bytes, hipMemcpyDeviceToHost, A->stream));
+    if (want_cells) HIPCHK(hipMemcpyAsync(pbig, dev + o_par, cell_bytes, hipMemcpyDeviceToHost, A->stream));
+    HIPCHK(wait_stream(A->stream));
+    intr_poll();
+    if (intr_raised()) return fail(LDSR_EINTERRUPTED, "interrupted by the caller's interrupt callback");
+    memcpy(winner, psel, sizeof(int) * (size_t)n_series);
+    memcpy(theta_w, psel + (o_thw - o_win), sizeof(double) * (size_t)n_series * P);
+    memcpy(value_w, psel + (o_vw - o_win), sizeof(double) * (size_t)n_series);
+    if (par_all) memcpy(par_all, pbig, sizeof(double) * (size_t)n_cells * P);
+    if (value_all) memcpy(value_all, pbig + (o_val - o_par), sizeof(double) * (size_t)n_cells);
+    if (n_iter_all) memcpy(n_iter_all, pbig + (o_nit - o_par), sizeof(int) * (size_t)n_cells);
+    if (n_eval_all) memcpy(n_eval_all, pbig + (o_nev - o_par), sizeof(int) * (size_t)n_cells);
+    if (status_all) memcpy(status_all, pbig + (o_st - o_par), sizeof(int) * (size_t)n_cells);
+    if (!want_fit) return LDSR_OK;
+
+    // the winners' fit: the series that have one, their thetas packed side by side
+    std::vector<int> ws_series;
+    std::vector<double> th((size_t)n_series * P);
+    for (int s = 0; s < n_series; s++)
+        if (winner[s] >= 0) {
+            memcpy(&th[ws_series.size() * P], theta_w + (size_t)s * P, sizeof(double) * (size_t)P);
+            ws_series.push_back(s);
+        }
+    const int n_w = (int)ws_series.size();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    auto fill = [&](double *a, size_t n) { if (a) std::fill(a, a + n, nan); };
+    if (n_w < n_series) {
+        fill(lik_w, (size_t)n_series); fill(X, nT); fill(Y, nT); fill(V, nT);
+        if (fit_mode == 1) fill(J, nT);
+    }
+    if (n_w == 0) return LDSR_OK;
+    char *ws = dev + o_ws;
+    HIPCHK(launch_series_prep(prep_params(n_series, T, p, q, PP, QQ, (const double *)(dev + U.o_y),
+                                          u ? (const double *)(dev + U.o_u) : nullptr,
+                                          v ? (const double *)(dev + U.o_v) : nullptr, shared_uv, ws, L, true),
+                              n_series, A->stream));
+    rc = stage_h2d_async(device, A->stream, dev + o_fth, th.data(), sizeof(double) * (size_t)n_w * P);
+    if (rc) return rc;
+    rc = launch_smoother(device, A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv, ws, L, n_w,
+                         ws_series, (const double *)(dev + o_fth), 1, fit_mode == 0 ? 1 : 0, 0.0,
+                         (double *)(dev + o_X), (double *)(dev + o_Y), (double *)(dev + o_V), (double *)(dev + o_J),
+                         (double *)(dev + o_lik), nullptr, (int *)(dev + o_fst), (int *)(dev + o_fsoc), false);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(pbig, dev + o_lik, fit_bytes, hipMemcpyDeviceToHost, A->stream));
+    HIPCHK(wait_stream(A->stream));
+    for (int i = 0; i < n_w; i++) {
+        const size_t s = (size_t)ws_series[(size_t)i], row = sizeof(double) * (size_t)i * T;
+        if (lik_w) lik_w[s] = ((const double *)pbig)[i];
+        if (X) memcpy(X + s * T, pbig + (o_X - o_lik) + row, sizeof(double) * (size_t)T);
+        if (Y) memcpy(Y + s * T, pbig + (o_Y - o_lik) + row, sizeof(double) * (size_t)T);
+        if (V) memcpy(V + s * T, pbig + (o_V - o_lik) + row, sizeof(double) * (size_t)T);
+        if (J && fit_mode == 1) memcpy(J + s * T, pbig + (o_J - o_lik) + row, sizeof(double) * (size_t)T);
+    }
     return LDSR_OK;
 }
 
