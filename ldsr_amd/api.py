@@ -112,6 +112,18 @@ def _series(y, u, v):
     return Y, U, V, S, T, p, q, shared
 
 
+def _offsets(cell_offsets, S, n):
+    """The [S+1] cell offsets of n cells as the C ABI takes them (default: one series owns every cell)."""
+    if cell_offsets is None:
+        if S != 1:
+            raise ValueError("cell_offsets is required with several series")
+        cell_offsets = [0, n]
+    off = np.ascontiguousarray(cell_offsets, dtype=np.int32)
+    if off.size != S + 1 or off[-1] != n:
+        raise ValueError("cell_offsets must have S+1 entries ending at n_cells")
+    return off
+
+
 def em_batch(y, u, v, theta0, cell_offsets=None, niter=1000, tol=1e-5, device=0, algo=ALGO_AUTO,
              return_liks=False, devices=None):
     """All cells in one launch.  theta0: packed [n_cells, 6+p+q].  cell_offsets: [S+1]
@@ -123,13 +135,7 @@ def em_batch(y, u, v, theta0, cell_offsets=None, niter=1000, tol=1e-5, device=0,
     if theta0.ndim != 2 or theta0.shape[1] != 6 + p + q:
         raise ValueError("theta0 must be [n_cells, %d]" % (6 + p + q))
     n = theta0.shape[0]
-    if cell_offsets is None:
-        if S != 1:
-            raise ValueError("cell_offsets is required with several series")
-        cell_offsets = [0, n]
-    off = np.ascontiguousarray(cell_offsets, dtype=np.int32)
-    if off.size != S + 1 or off[-1] != n:
-        raise ValueError("cell_offsets must have S+1 entries ending at n_cells")
+    off = _offsets(cell_offsets, S, n)
     theta = np.empty_like(theta0)
     lik = np.empty(n)
     n_iter = np.empty(n, dtype=np.int32)
@@ -248,13 +254,7 @@ def em_restart_grid(y, u, v, theta0, cell_offsets=None, niter=1000, tol=1e-5, de
     if theta0.ndim != 2 or theta0.shape[1] != P:
         raise ValueError("theta0 must be [n_cells, %d]" % P)
     n = theta0.shape[0]
-    if cell_offsets is None:
-        if S != 1:
-            raise ValueError("cell_offsets is required with several series")
-        cell_offsets = [0, n]
-    off = np.ascontiguousarray(cell_offsets, dtype=np.int32)
-    if off.size != S + 1 or off[-1] != n:
-        raise ValueError("cell_offsets must have S+1 entries ending at n_cells")
+    off = _offsets(cell_offsets, S, n)
     devs = np.ascontiguousarray(devices, dtype=np.int32)
     out, allr = _grid_outputs(S, T, P, n, int(niter), return_all)
     a = allr or {}

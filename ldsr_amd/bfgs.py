@@ -11,21 +11,10 @@ or of the optimiser."""
 import numpy as np
 
 from . import _lib
-from .api import _d, _dims, _i, _series, unpack_theta
+from .api import _d, _dims, _i, _offsets, _series, unpack_theta
 
 CONVERGED, MAXIT, LINESEARCH, NONFINITE, INTERRUPTED = 0, 1, 2, 3, 4
 _START_STREAM = 1 << 40       # counter-mode stream of restart r: _START_STREAM + r
-
-
-def _offsets(cell_offsets, S, n):
-    if cell_offsets is None:
-        if S != 1:
-            raise ValueError("cell_offsets is required with several series")
-        cell_offsets = [0, n]
-    off = np.ascontiguousarray(cell_offsets, dtype=np.int32)
-    if off.size != S + 1 or off[-1] != n:
-        raise ValueError("cell_offsets must have S+1 entries ending at n_cells")
-    return off
 
 
 def ssq_train(y, u, v, theta_packed, cell_offsets=None, grad=False, device=0):

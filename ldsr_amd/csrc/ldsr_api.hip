@@ -485,6 +485,16 @@ static int check_em(int niter, double tol) {
     return LDSR_OK;
 }
 
+static int check_box(const double *lb, const double *ub, int P, const char *noun) {
+    if (!lb || !ub) return fail(LDSR_EINVAL, "lb and ub must not be NULL");
+    for (int c = 0; c < P; c++) {
+        if (!std::isfinite(lb[c]) || !std::isfinite(ub[c]) || !std::isfinite(ub[c] - lb[c]))
+            return fail(LDSR_EINVAL, "lb and ub must be finite");
+        if (lb[c] > ub[c]) return fail(LDSR_EINVAL, std::string("lb must be <= ub in every ") + noun);
+    }
+    return LDSR_OK;
+}
+
 extern "C" size_t ldsr_em_workspace_bytes(int n_series, int T, int p, int q, int n_cells,
                                           int algo) {
     if (n_series < 1 || n_cells < 0) return 0;
@@ -721,6 +731,34 @@ extern "C" int ldsr_em_batch_device(int device, void *stream_, int n_series, int
                                      d_status, d_liks, d_workspace, workspace_bytes, 0);
 }
 
+// Series that series_prep has prepared in the workspace ws (layout *L); what reads them goes on `stream`
+struct PreparedSeries {
+    int device;
+    hipStream_t stream;
+    int T, p, q, PP, QQ, shared_uv;
+    bool has_u, has_v;
+    char *ws;
+    const WsLayout *L;
+};
+
+// Where a smoother pass writes, on the device: rows [n][T] of X, Y, V, J and [n] of lik, pen, status.  pen set:
+// only the scalars leave the kernel, and X and V are the serial smoother's filtered-state strip.
+struct FitOut {
+    double *X = nullptr, *Y = nullptr, *V = nullptr, *J = nullptr, *lik = nullptr, *pen = nullptr;
+    int *status = nullptr;
+};
+
+// the prepared-series fields of a kernel's parameters (EmParams, SmoothParams)
+template <class Params>
+static void set_prepared_series(Params &prm, const PreparedSeries &S) {
+    prm.T = S.T; prm.p = S.p; prm.q = S.q; prm.has_u = S.has_u; prm.has_v = S.has_v;
+    prm.yp = (const double *)(S.ws + S.L->yp);
+    prm.up = (const double *)(S.ws + S.L->up);
+    prm.vp = (const double *)(S.ws + S.L->vp);
+    prm.u_stride = S.shared_uv ? 0 : (long)S.T * S.PP; prm.v_stride = S.shared_uv ? 0 : (long)S.T * S.QQ;
+    prm.sc = (const SeriesConst *)(S.ws + S.L->sc);
+}
+
 // One Kalman_smoother pass (src/EM.cpp:22-131) for n cells on prepared series: the FIT form of
 // the scan kernel (one wave group per cell) whenever the shape is supported, else the serial
 // one-thread-per-cell kernel.  mode: 0 smoother, 1 propagate (serial kernel only).
@@ -739,113 +777,90 @@ static bool smoother_is_scan(int T, int PP, int QQ, const WsLayout &L, int mode)
 
 // The scan launch's block table (series, first cell, cells; blocks never straddle a series) into the
 // workspace, or the serial kernel's cell -> series map into d_soc; both through the pinned staging ring.
-static int smoother_tables(int device, hipStream_t stream, int T, int PP, int QQ, char *ws, const WsLayout &L,
-                           int n, const std::vector<int> &series_of_cell, int mode, int *d_soc,
+static int smoother_tables(const PreparedSeries &S, int n, const int *series_of_cell, int mode, int *d_soc,
                            SmootherTables *out, const std::vector<char> *skip_series = nullptr) {
-    out->scan = smoother_is_scan(T, PP, QQ, L, mode);
-    if (!out->scan) return stage_h2d_async(device, stream, d_soc, series_of_cell.data(), sizeof(int) * (size_t)n);
-    const int cpb = em_scan_cells_per_block(T, PP, QQ);
+    out->scan = smoother_is_scan(S.T, S.PP, S.QQ, *S.L, mode);
+    if (!out->scan) return stage_h2d_async(S.device, S.stream, d_soc, series_of_cell, sizeof(int) * (size_t)n);
+    const int cpb = em_scan_cells_per_block(S.T, S.PP, S.QQ);
     std::vector<int> tab, bc, bn;           // (tab: the series column, then the other two)
     for (int c = 0; c < n;) {
-        if (skip_series && (*skip_series)[(size_t)series_of_cell[(size_t)c]]) {      // (the caller runs these cells itself)
+        if (skip_series && (*skip_series)[(size_t)series_of_cell[c]]) {      // (the caller runs these cells itself)
             c++;
             continue;
         }
         int e = c + 1;
-        while (e < n && e - c < cpb && series_of_cell[(size_t)e] == series_of_cell[(size_t)c]) e++;
-        tab.push_back(series_of_cell[(size_t)c]);
+        while (e < n && e - c < cpb && series_of_cell[e] == series_of_cell[c]) e++;
+        tab.push_back(series_of_cell[c]);
         bc.push_back(c);
         bn.push_back(e - c);
         c = e;
     }
     out->n_blocks = (int)tab.size();
-    if (out->n_blocks > L.max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow (fit)");
+    if (out->n_blocks > S.L->max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow (fit)");
     if (out->n_blocks == 0) return LDSR_OK;
     tab.insert(tab.end(), bc.begin(), bc.end());
     tab.insert(tab.end(), bn.begin(), bn.end());
-    int *d_ws_tab = (int *)(ws + L.blk);
+    int *d_ws_tab = (int *)(S.ws + S.L->blk);
     out->d_tab = d_ws_tab;
-    return stage_h2d_async(device, stream, d_ws_tab, tab.data(), sizeof(int) * tab.size());
+    return stage_h2d_async(S.device, S.stream, d_ws_tab, tab.data(), sizeof(int) * tab.size());
 }
 
-static int smoother_enqueue(hipStream_t stream, int T, int p, int q, int PP, int QQ, bool has_u, bool has_v,
-                            int shared_uv, char *ws, const WsLayout &L, int n, const SmootherTables &tb,
-                            const double *d_theta, int stdlik, int mode, double lambda, double *d_X,
-                            double *d_Y, double *d_V, double *d_J, double *d_lik, double *d_pen,
-                            int *d_status, const int *d_soc, bool scalar_only) {
+static int smoother_enqueue(const PreparedSeries &S, int n, const SmootherTables &tb, const int *d_soc,
+                            const double *d_theta, int stdlik, int mode, double lambda, const FitOut &out) {
+    const bool scalar_only = out.pen != nullptr;
     if (tb.scan) {
         const int *d_tab = tb.d_tab;
         const int n_blocks = tb.n_blocks;
         if (n_blocks == 0) return LDSR_OK;
         EmParams prm;
         memset(&prm, 0, sizeof(prm));
-        prm.T = T; prm.p = p; prm.q = q; prm.has_u = has_u; prm.has_v = has_v;
+        set_prepared_series(prm, S);
         prm.niter = 1; prm.n_cells = n; prm.tol = 0.0;
-        prm.yp = (const double *)(ws + L.yp);
-        prm.yz = (const double *)(ws + L.yz);
-        prm.up = (const double *)(ws + L.up);
-        prm.vp = (const double *)(ws + L.vp);
-        prm.u_stride = shared_uv ? 0 : (long)T * PP;
-        prm.v_stride = shared_uv ? 0 : (long)T * QQ;
-        prm.img = (const double *)(ws + L.img);
-        prm.img_stride = L.img_stride;
-        prm.sc = (const SeriesConst *)(ws + L.sc);
+        prm.yz = (const double *)(S.ws + S.L->yz);
+        prm.img = (const double *)(S.ws + S.L->img);
+        prm.img_stride = S.L->img_stride;
         prm.blk_series = d_tab;
         prm.blk_cell0 = d_tab + n_blocks;
         prm.blk_ncell = d_tab + 2 * n_blocks;
-        prm.queue = (int *)(ws + L.queue);
+        prm.queue = (int *)(S.ws + S.L->queue);
         prm.theta0 = d_theta;
-        prm.lik = d_lik;
-        prm.status = d_status;
-        prm.fitX = scalar_only ? nullptr : d_X; prm.fitY = scalar_only ? nullptr : d_Y;
-        prm.fitV = scalar_only ? nullptr : d_V; prm.fitJ = scalar_only ? nullptr : d_J;
-        prm.pen = d_pen;
+        prm.lik = out.lik; prm.pen = out.pen; prm.status = out.status;
+        prm.fitX = scalar_only ? nullptr : out.X; prm.fitY = scalar_only ? nullptr : out.Y;
+        prm.fitV = scalar_only ? nullptr : out.V; prm.fitJ = scalar_only ? nullptr : out.J;
         prm.lambda = lambda;
         prm.stdlik = stdlik;
-        HIPCHK(launch_em_scan(prm, PP, QQ, n_blocks, false, true, stream));
+        HIPCHK(launch_em_scan(prm, S.PP, S.QQ, n_blocks, false, true, S.stream));
         return LDSR_OK;
     }
     SmoothParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.T = T; sp.p = p; sp.q = q; sp.has_u = has_u; sp.has_v = has_v;
+    set_prepared_series(sp, S);
     sp.n_cells = n; sp.stdlik = stdlik; sp.mode = mode;
     sp.lambda = lambda;
-    sp.yp = (const double *)(ws + L.yp);
-    sp.up = (const double *)(ws + L.up);
-    sp.vp = (const double *)(ws + L.vp);
-    sp.u_stride = shared_uv ? 0 : (long)T * PP;
-    sp.v_stride = shared_uv ? 0 : (long)T * QQ;
-    sp.sc = (const SeriesConst *)(ws + L.sc);
     sp.series_of_cell = d_soc;
     sp.theta = d_theta;
-    sp.X = d_X; sp.Y = d_Y; sp.V = d_V; sp.J = d_J;
-    sp.lik = d_lik;
-    sp.status = d_status;
-    sp.pen = d_pen;
+    sp.X = out.X; sp.Y = out.Y; sp.V = out.V; sp.J = out.J;
+    sp.lik = out.lik; sp.pen = out.pen; sp.status = out.status;
     sp.scalar_only = scalar_only;
-    HIPCHK(launch_smooth(sp, PP, QQ, stream));
+    HIPCHK(launch_smooth(sp, S.PP, S.QQ, S.stream));
     return LDSR_OK;
 }
 
 // Both parts for a one-off pass.  d_tab_prebuilt: a block table [3][n], one block per cell, that the
 // device filled itself (the restart grid's winners).
-static int launch_smoother(int device, hipStream_t stream, int T, int p, int q, int PP, int QQ,
-                           bool has_u, bool has_v, int shared_uv, char *ws, const WsLayout &L,
-                           int n, const std::vector<int> &series_of_cell, const double *d_theta,
-                           int stdlik, int mode, double lambda, double *d_X, double *d_Y,
-                           double *d_V, double *d_J, double *d_lik, double *d_pen, int *d_status,
-                           int *d_soc, bool scalar_only, const int *d_tab_prebuilt = nullptr) {
+static int launch_smoother(const PreparedSeries &S, int n, const int *series_of_cell, const double *d_theta,
+                           int stdlik, int mode, double lambda, const FitOut &out, int *d_soc,
+                           const int *d_tab_prebuilt = nullptr) {
     SmootherTables tb;
-    if (d_tab_prebuilt && smoother_is_scan(T, PP, QQ, L, mode)) {
+    if (d_tab_prebuilt && smoother_is_scan(S.T, S.PP, S.QQ, *S.L, mode)) {
         tb.scan = true;
         tb.d_tab = d_tab_prebuilt;
         tb.n_blocks = n;
     } else {
-        const int rc = smoother_tables(device, stream, T, PP, QQ, ws, L, n, series_of_cell, mode, d_soc, &tb);
+        const int rc = smoother_tables(S, n, series_of_cell, mode, d_soc, &tb);
         if (rc) return rc;
     }
-    return smoother_enqueue(stream, T, p, q, PP, QQ, has_u, has_v, shared_uv, ws, L, n, tb, d_theta, stdlik,
-                            mode, lambda, d_X, d_Y, d_V, d_J, d_lik, d_pen, d_status, d_soc, scalar_only);
+    return smoother_enqueue(S, n, tb, d_soc, d_theta, stdlik, mode, lambda, out);
 }
 
 // ---- one contiguous slice of the cell grid on one device ---------------------------------------
@@ -924,6 +939,17 @@ static WinLayout win_layout(int n, int P, int T, int niter) {
     W.out_bytes = c.o - W.out_begin;
     W.total = c.o;
     return W;
+}
+
+// the winners' fit of a slice: one pass at the n thetas of its phase-2 block dw, on the series phase 1 prepared in ws
+static int slice_fit(const Slice &S, char *ws, char *dw, const WinLayout &W, int n, const int *series_of_cell,
+                     const int *d_tab_prebuilt = nullptr) {
+    const PreparedSeries PS{S.device, S.lease.a->stream, S.T, S.p, S.q, S.PP, S.QQ, S.shared_uv, S.u != nullptr,
+                            S.v != nullptr, ws, &S.L};
+    const FitOut F{(double *)(dw + W.X), (double *)(dw + W.Y), (double *)(dw + W.V), (double *)(dw + W.J),
+                   (double *)(dw + W.lik), nullptr, (int *)(dw + W.st)};
+    return launch_smoother(PS, n, series_of_cell, (const double *)(dw + W.theta), 1, 0, 0.0, F, (int *)(dw + W.ser),
+                           d_tab_prebuilt);
 }
 
 // per-cell results of the slice (pinned block `pout`) -> the caller's arrays, series by series
@@ -1069,12 +1095,7 @@ static int slice_run(Slice &S) {
             std::vector<int> soc((size_t)ns);
             for (int i = 0; i < ns; i++) soc[(size_t)i] = i;
             char *ws = A->dev + S.d_ws;
-            rc = launch_smoother(S.device, A->stream, T, S.p, S.q, S.PP, S.QQ, S.u != nullptr,
-                                 S.v != nullptr, S.shared_uv, ws, S.L, ns, soc,
-                                 (const double *)(dw + W.theta), 1, 0, 0.0, (double *)(dw + W.X),
-                                 (double *)(dw + W.Y), (double *)(dw + W.V), (double *)(dw + W.J),
-                                 (double *)(dw + W.lik), nullptr, (int *)(dw + W.st),
-                                 (int *)(dw + W.ser), false, (const int *)(dw + W.blk));
+            rc = slice_fit(S, ws, dw, W, ns, soc.data(), (const int *)(dw + W.blk));
             if (rc) return rc;
         }
         if (S.want_all)
@@ -1163,12 +1184,7 @@ static int slice_fit_winners(Slice &S, int n_w, const int *w_series, const int *
     // the winners' fit: one smoother pass at theta_w on the prepared series
     if (X || Y || V || J) {
         std::vector<int> soc(w_series, w_series + n_w);
-        int rc = launch_smoother(S.device, A->stream, T, S.p, S.q, S.PP, S.QQ, S.u != nullptr,
-                                 S.v != nullptr, S.shared_uv, ws, S.L, n_w, soc,
-                                 (const double *)(dw + W.theta), 1, 0, 0.0, (double *)(dw + W.X),
-                                 (double *)(dw + W.Y), (double *)(dw + W.V), (double *)(dw + W.J),
-                                 (double *)(dw + W.lik), nullptr, (int *)(dw + W.st),
-                                 (int *)(dw + W.ser), false);
+        int rc = slice_fit(S, ws, dw, W, n_w, soc.data());
         if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(pw + W.out_begin, dw + W.out_begin, W.out_bytes, hipMemcpyDeviceToHost,
@@ -1432,111 +1448,146 @@ extern "C" int ldsr_em_restart_groups(int n_devices, const int *devices, int n_g
     return LDSR_OK;
 }
 
-// ---- smoother / propagate / mstep / penalized likelihood host entry points ---------------------
-// mode: 0 smoother, 1 propagate, 2 mstep, 3 penalized likelihood (smoother, scalar output only)
-static int run_fit_kernel(int mode, int device, int n_series, int T, int p, int q, const double *y,
-                          const double *u, const double *v, int shared_uv,
-                          const int *cell_offsets, const double *theta_in, int stdlik, double *X,
-                          double *Y, double *V, double *J, double *lik, double *theta_out,
-                          int *status, double lambda = 0.0) {
-    int rc = check_common(n_series, T, p, q, y, cell_offsets);
-    if (rc) return rc;
-    const int n_cells = cell_offsets[n_series];
-    if (n_cells == 0) return LDSR_OK;
-    if (mode == 2 && (!X || !V || !J || !theta_out)) return fail(LDSR_EINVAL, "mstep needs X, V, J and theta");
-    if (mode != 2 && (!theta_in || !lik)) return fail(LDSR_EINVAL, "theta and lik must not be NULL");
-    const int P = 6 + p + q;
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
-    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
-    const size_t nT = (size_t)n_cells * T;
-    const bool scalar_only = mode == 3;     // only [n_cells] scalars leave the device
-    ArenaLease lease;
-    rc = arena_acquire(device, &lease.a);
-    if (rc) return rc;
-    Arena *A = lease.a;
-    const WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_cells, LDSR_ALGO_SCAN, 1);
-    // the serial smoother uses X / V as its filtered-state strip; the scan FIT kernel needs none
-    const bool need_strip = !(mode == 0 || mode == 3) || !em_scan_supported(T, PP, QQ);
-    Carver c;
-    const size_t o_y = c.take(sizeof(double) * (size_t)n_series * T);
-    const size_t o_u = c.take(u ? sizeof(double) * nuv * T * p : 0);
-    const size_t o_v = c.take(v ? sizeof(double) * nuv * T * q : 0);
-    const size_t o_th = c.take(sizeof(double) * (size_t)n_cells * P);
-    const size_t o_soc = c.take(sizeof(int) * (size_t)n_cells);
-    const size_t in_bytes = c.o;
-    const size_t o_lik = c.take(sizeof(double) * (size_t)n_cells);
-    const size_t o_pen = c.take(sizeof(double) * (size_t)n_cells);
-    const size_t o_st = c.take(sizeof(int) * (size_t)n_cells);
-    const size_t o_tho = c.take(sizeof(double) * (size_t)n_cells * P);
-    const size_t small_out = c.o - o_lik;
-    const size_t o_X = c.take((scalar_only && !need_strip) ? 0 : sizeof(double) * nT);
-    const size_t o_V = c.take((scalar_only && !need_strip) ? 0 : sizeof(double) * nT);
-    const size_t o_Y = c.take(scalar_only ? 0 : sizeof(double) * nT);
-    const size_t o_J = c.take(scalar_only ? 0 : sizeof(double) * nT);
-    const size_t o_ws = c.take(L.total);
-    rc = arena_reserve(A, c.o, in_bytes + align256(small_out));
-    if (rc) return rc;
-    char *dev = A->dev, *pin = A->pin;
-    memcpy(pin + o_y, y, sizeof(double) * (size_t)n_series * T);
-    if (u) memcpy(pin + o_u, u, sizeof(double) * nuv * T * p);
-    if (v) memcpy(pin + o_v, v, sizeof(double) * nuv * T * q);
-    if (theta_in) memcpy(pin + o_th, theta_in, sizeof(double) * (size_t)n_cells * P);
-    int *soc = (int *)(pin + o_soc);
-    for (int s = 0; s < n_series; s++)
-        for (int cc = cell_offsets[s]; cc < cell_offsets[s + 1]; cc++) soc[cc] = s;
-    HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
-    char *ws = dev + o_ws;
-    HIPCHK(launch_series_prep(prep_params(n_series, T, p, q, PP, QQ, (const double *)(dev + o_y),
-                                          u ? (const double *)(dev + o_u) : nullptr,
-                                          v ? (const double *)(dev + o_v) : nullptr, shared_uv, ws, L, true),
-                              n_series, A->stream));
+// ---- what the host-pointer entries of the smoother, GA and BFGS families share ----------------
+// The series of a call as they cross the ABI (u, v null: absent) and their part of its input block: carve() takes
+// y | u | v and, given cell_offsets, the cell -> series map and the theta rows; stage() fills them in the pinned
+// block and says where the caller's ONE copy of its whole input block puts them on the device.
+struct SeriesUpload {
+    int n_series, T, p, q;
+    const double *y, *u, *v;
+    int shared_uv;
+    const int *cell_offsets = nullptr;
+    const double *theta = nullptr;      // (null with cell_offsets: the rows are reserved and go up as they are)
+    size_t o_y = 0, o_u = 0, o_v = 0, o_soc = 0, o_th = 0;
+    const double *d_y = nullptr, *d_u = nullptr, *d_v = nullptr, *d_theta = nullptr;
+    int *d_soc = nullptr, *h_soc = nullptr;     // (h_soc: the staged map, for the block tables)
+    PreparedSeries ps;                          // prep(): the series as series_prep leaves them
+    size_t uv_bytes(const double *a, int k) const { return a ? sizeof(double) * (shared_uv ? 1 : (size_t)n_series) * T * k : 0; }
+    void carve(Carver &c, const int *offsets = nullptr, const double *theta_rows = nullptr) {
+        cell_offsets = offsets; theta = theta_rows;
+        o_y = c.take(sizeof(double) * (size_t)n_series * T);
+        o_u = c.take(uv_bytes(u, p));
+        o_v = c.take(uv_bytes(v, q));
+        if (!offsets) return;
+        o_soc = c.take(sizeof(int) * (size_t)offsets[n_series]);
+        o_th = c.take(sizeof(double) * (size_t)offsets[n_series] * (6 + p + q));
+    }
+    void stage(const Arena *A) {
+        memcpy(A->pin + o_y, y, sizeof(double) * (size_t)n_series * T);
+        if (u) memcpy(A->pin + o_u, u, uv_bytes(u, p));
+        if (v) memcpy(A->pin + o_v, v, uv_bytes(v, q));
+        d_y = (const double *)(A->dev + o_y);
+        d_u = u ? (const double *)(A->dev + o_u) : nullptr;
+        d_v = v ? (const double *)(A->dev + o_v) : nullptr;
+        if (!cell_offsets) return;
+        h_soc = (int *)(A->pin + o_soc); d_soc = (int *)(A->dev + o_soc); d_theta = (const double *)(A->dev + o_th);
+        for (int s = 0; s < n_series; s++)
+            for (int cc = cell_offsets[s]; cc < cell_offsets[s + 1]; cc++) h_soc[cc] = s;
+        if (theta) memcpy(A->pin + o_th, theta, sizeof(double) * (size_t)cell_offsets[n_series] * (6 + p + q));
+    }
+    // series_prep of the uploaded series into the workspace ws (layout *L)
+    hipError_t prep(int device, hipStream_t stream, char *ws, const WsLayout *L) {
+        ps = PreparedSeries{device, stream, T, p, q, ldsr_pad_dim(p), ldsr_pad_dim(q), shared_uv, u != nullptr, v != nullptr,
+                            ws, L};
+        return launch_series_prep(prep_params(n_series, T, p, q, ps.PP, ps.QQ, d_y, d_u, d_v, shared_uv, ws, *L, true),
+                                  n_series, stream);
+    }
+};
 
-    std::vector<int> soc_v(soc, soc + n_cells);
-    char *pout = pin + in_bytes;
-    if (mode == 2) {
-        // the fit arrives from the caller: X, V, J rows straight into the device arrays
-        HIPCHK(hipMemcpyAsync(dev + o_X, X, sizeof(double) * nT, hipMemcpyHostToDevice, A->stream));
-        HIPCHK(hipMemcpyAsync(dev + o_V, V, sizeof(double) * nT, hipMemcpyHostToDevice, A->stream));
-        HIPCHK(hipMemcpyAsync(dev + o_J, J, sizeof(double) * nT, hipMemcpyHostToDevice, A->stream));
-        SmoothParams sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.T = T; sp.p = p; sp.q = q; sp.has_u = u != nullptr; sp.has_v = v != nullptr;
-        sp.n_cells = n_cells;
-        sp.yp = (const double *)(ws + L.yp);
-        sp.up = (const double *)(ws + L.up);
-        sp.vp = (const double *)(ws + L.vp);
-        sp.u_stride = shared_uv ? 0 : (long)T * PP;
-        sp.v_stride = shared_uv ? 0 : (long)T * QQ;
-        sp.sc = (const SeriesConst *)(ws + L.sc);
-        sp.series_of_cell = (const int *)(dev + o_soc);
-        sp.X = (double *)(dev + o_X); sp.V = (double *)(dev + o_V); sp.J = (double *)(dev + o_J);
-        sp.status = (int *)(dev + o_st);
-        sp.theta_out = (double *)(dev + o_tho);
-        HIPCHK(launch_mstep(sp, PP, QQ, A->stream));
-        HIPCHK(hipMemcpyAsync(pout, dev + o_lik, small_out, hipMemcpyDeviceToHost, A->stream));
-        HIPCHK(hipStreamSynchronize(A->stream));
-        memcpy(theta_out, pout + (o_tho - o_lik), sizeof(double) * (size_t)n_cells * P);
-        if (status) memcpy(status, pout + (o_st - o_lik), sizeof(int) * (size_t)n_cells);
+// ---- smoother / propagate / mstep / penalized likelihood host entry points ---------------------
+enum FitKind { FIT_SMOOTH, FIT_PROPAGATE, FIT_MSTEP, FIT_PENLIK };     // (PENLIK: only lik - lambda * ssq leaves the device)
+
+// The arena block of one such call, uploaded and prepared (begin): [series | map | theta] go up in one copy;
+// d.lik, d.pen, d.status and d_theta_out come back in one (small_out bytes, host() says where); the rows stay.
+struct FitCall {
+    ArenaLease lease;
+    WsLayout L;
+    SeriesUpload U;
+    size_t n_cells, row_bytes, small_out;
+    FitOut d;       // (d.pen: FIT_PENLIK only)
+    double *d_theta_out;
+    char *pout;     // (pinned: the small outputs)
+
+    const char *host(const void *small) const { return pout + ((const char *)small - (const char *)d.lik); }
+    // (the serial kernels use X / V as their filtered-state strip; only FIT_PENLIK writes no rows)
+    int begin(FitKind kind, int device, const SeriesUpload &series, const int *cell_offsets, const double *theta) {
+        U = series;
+        int rc = arena_acquire(device, &lease.a);
+        if (rc) return rc;
+        Arena *A = lease.a;
+        const int PP = ldsr_pad_dim(U.p), QQ = ldsr_pad_dim(U.q);
+        n_cells = (size_t)cell_offsets[U.n_series]; row_bytes = sizeof(double) * n_cells * U.T;
+        L = ws_layout(U.n_series, U.T, PP, QQ, U.shared_uv, (int)n_cells, LDSR_ALGO_SCAN, 1);
+        const bool need_strip = kind == FIT_PROPAGATE || kind == FIT_MSTEP || !em_scan_supported(U.T, PP, QQ);
+        const size_t yj_bytes = kind == FIT_PENLIK ? 0 : row_bytes, xv_bytes = need_strip ? row_bytes : yj_bytes;
+        Carver c;
+        U.carve(c, cell_offsets, theta);
+        const size_t in_bytes = c.o;
+        const size_t o_lik = c.take(sizeof(double) * n_cells), o_pen = c.take(sizeof(double) * n_cells);
+        const size_t o_st = c.take(sizeof(int) * n_cells), o_tho = c.take(sizeof(double) * n_cells * (6 + U.p + U.q));
+        small_out = c.o - o_lik;
+        const size_t o_X = c.take(xv_bytes), o_V = c.take(xv_bytes), o_Y = c.take(yj_bytes), o_J = c.take(yj_bytes);
+        const size_t o_ws = c.take(L.total);
+        rc = arena_reserve(A, c.o, in_bytes + align256(small_out));
+        if (rc) return rc;
+        char *dev = A->dev;
+        pout = A->pin + in_bytes;
+        d.X = (double *)(dev + o_X); d.Y = (double *)(dev + o_Y); d.V = (double *)(dev + o_V); d.J = (double *)(dev + o_J);
+        d.lik = (double *)(dev + o_lik); d.status = (int *)(dev + o_st); d_theta_out = (double *)(dev + o_tho);
+        d.pen = kind == FIT_PENLIK ? (double *)(dev + o_pen) : nullptr;
+        U.stage(A);
+        HIPCHK(hipMemcpyAsync(dev, A->pin, in_bytes, hipMemcpyHostToDevice, A->stream));
+        HIPCHK(U.prep(device, A->stream, dev + o_ws, &L));
         return LDSR_OK;
     }
-    rc = launch_smoother(device, A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv,
-                         ws, L, n_cells, soc_v, (const double *)(dev + o_th), stdlik,
-                         mode == 1 ? 1 : 0, lambda, (double *)(dev + o_X), (double *)(dev + o_Y),
-                         (double *)(dev + o_V), (double *)(dev + o_J), (double *)(dev + o_lik),
-                         scalar_only ? (double *)(dev + o_pen) : nullptr, (int *)(dev + o_st),
-                         (int *)(dev + o_soc), scalar_only);
+};
+
+// Mstep (src/EM.cpp:139-229): the fit arrives from the caller, its X, V, J rows go straight into the device arrays
+static int run_mstep(int device, const SeriesUpload &U, const int *cell_offsets, const double *X, const double *V,
+                     const double *J, double *theta_out, int *status) {
+    int rc = check_common(U.n_series, U.T, U.p, U.q, U.y, cell_offsets);
+    if (rc || cell_offsets[U.n_series] == 0) return rc;
+    if (!X || !V || !J || !theta_out) return fail(LDSR_EINVAL, "mstep needs X, V, J and theta");
+    FitCall F;
+    rc = F.begin(FIT_MSTEP, device, U, cell_offsets, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(pout, dev + o_lik, small_out, hipMemcpyDeviceToHost, A->stream));
-    HIPCHK(hipStreamSynchronize(A->stream));
-    if (scalar_only) {
-        memcpy(lik, pout + (o_pen - o_lik), sizeof(double) * (size_t)n_cells);
-        return LDSR_OK;
-    }
-    memcpy(lik, pout, sizeof(double) * (size_t)n_cells);
-    if (X) HIPCHK(hipMemcpy(X, dev + o_X, sizeof(double) * nT, hipMemcpyDeviceToHost));
-    if (Y) HIPCHK(hipMemcpy(Y, dev + o_Y, sizeof(double) * nT, hipMemcpyDeviceToHost));
-    if (V) HIPCHK(hipMemcpy(V, dev + o_V, sizeof(double) * nT, hipMemcpyDeviceToHost));
-    if (J && mode == 0) HIPCHK(hipMemcpy(J, dev + o_J, sizeof(double) * nT, hipMemcpyDeviceToHost));
+    SmoothParams sp;
+    memset(&sp, 0, sizeof(sp));
+    set_prepared_series(sp, F.U.ps);
+    sp.n_cells = (int)F.n_cells; sp.series_of_cell = F.U.d_soc;
+    sp.X = F.d.X; sp.V = F.d.V; sp.J = F.d.J; sp.status = F.d.status; sp.theta_out = F.d_theta_out;
+    HIPCHK(hipMemcpyAsync(sp.X, X, F.row_bytes, hipMemcpyHostToDevice, F.U.ps.stream));
+    HIPCHK(hipMemcpyAsync(sp.V, V, F.row_bytes, hipMemcpyHostToDevice, F.U.ps.stream));
+    HIPCHK(hipMemcpyAsync(sp.J, J, F.row_bytes, hipMemcpyHostToDevice, F.U.ps.stream));
+    HIPCHK(launch_mstep(sp, F.U.ps.PP, F.U.ps.QQ, F.U.ps.stream));
+    HIPCHK(hipMemcpyAsync(F.pout, F.d.lik, F.small_out, hipMemcpyDeviceToHost, F.U.ps.stream));
+    HIPCHK(hipStreamSynchronize(F.U.ps.stream));
+    memcpy(theta_out, F.host(F.d_theta_out), sizeof(double) * F.n_cells * (6 + U.p + U.q));
+    if (status) memcpy(status, F.host(F.d.status), sizeof(int) * F.n_cells);
+    return LDSR_OK;
+}
+
+// host: the caller's arrays, null where a row is not wanted (lik: for FIT_PENLIK the penalised likelihood)
+static int run_fit_kernel(FitKind kind, int device, const SeriesUpload &U, const int *cell_offsets,
+                          const double *theta, int stdlik, double lambda, const FitOut &host) {
+    int rc = check_common(U.n_series, U.T, U.p, U.q, U.y, cell_offsets);
+    if (rc || cell_offsets[U.n_series] == 0) return rc;
+    if (!theta || !host.lik) return fail(LDSR_EINVAL, "theta and lik must not be NULL");
+    FitCall F;
+    rc = F.begin(kind, device, U, cell_offsets, theta);
+    if (rc) return rc;
+    const FitOut &d = F.d;
+    rc = launch_smoother(F.U.ps, (int)F.n_cells, F.U.h_soc, F.U.d_theta, stdlik, kind == FIT_PROPAGATE ? 1 : 0,
+                         lambda, d, F.U.d_soc);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(F.pout, d.lik, F.small_out, hipMemcpyDeviceToHost, F.U.ps.stream));
+    HIPCHK(hipStreamSynchronize(F.U.ps.stream));
+    memcpy(host.lik, F.host(d.pen ? d.pen : d.lik), sizeof(double) * F.n_cells);
+    if (d.pen) return LDSR_OK;
+    if (host.X) HIPCHK(hipMemcpy(host.X, d.X, F.row_bytes, hipMemcpyDeviceToHost));
+    if (host.Y) HIPCHK(hipMemcpy(host.Y, d.Y, F.row_bytes, hipMemcpyDeviceToHost));
+    if (host.V) HIPCHK(hipMemcpy(host.V, d.V, F.row_bytes, hipMemcpyDeviceToHost));
+    if (host.J) HIPCHK(hipMemcpy(host.J, d.J, F.row_bytes, hipMemcpyDeviceToHost));
     return LDSR_OK;
 }
 
@@ -1544,16 +1595,32 @@ extern "C" int ldsr_smooth_batch(int device, int n_series, int T, int p, int q, 
                                  const double *u, const double *v, int shared_uv,
                                  const int *cell_offsets, const double *theta, int stdlik,
                                  double *X, double *Y, double *V, double *J, double *lik) {
-    return run_fit_kernel(0, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta,
-                          stdlik, X, Y, V, J, lik, nullptr, nullptr);
+    return run_fit_kernel(FIT_SMOOTH, device, SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets,
+                          theta, stdlik, 0.0, FitOut{X, Y, V, J, lik});
+}
+
+extern "C" int ldsr_propagate_batch(int device, int n_series, int T, int p, int q, const double *y,
+                                    const double *u, const double *v, int shared_uv,
+                                    const int *cell_offsets, const double *theta, int stdlik,
+                                    double *X, double *Y, double *V, double *lik) {
+    return run_fit_kernel(FIT_PROPAGATE, device, SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets,
+                          theta, stdlik, 0.0, FitOut{X, Y, V, nullptr, lik});
 }
 
 extern "C" int ldsr_penalized_lik_batch(int device, int n_series, int T, int p, int q,
                                         const double *y, const double *u, const double *v,
                                         int shared_uv, const int *cell_offsets, const double *theta,
                                         double lambda, double *pl) {
-    return run_fit_kernel(3, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta, 0,
-                          nullptr, nullptr, nullptr, nullptr, pl, nullptr, nullptr, lambda);
+    return run_fit_kernel(FIT_PENLIK, device, SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets,
+                          theta, 0, lambda, FitOut{nullptr, nullptr, nullptr, nullptr, pl});
+}
+
+extern "C" int ldsr_mstep_batch(int device, int n_series, int T, int p, int q, const double *y,
+                                const double *u, const double *v, int shared_uv,
+                                const int *cell_offsets, const double *X, const double *V,
+                                const double *J, double *theta, int *status) {
+    return run_mstep(device, SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets, X, V, J, theta,
+                     status);
 }
 
 // ---- LDS_GA: the island genetic algorithm (ga.hip) ------------------------------------------------
@@ -1580,12 +1647,8 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
     int rc = check_common(n_series, T, p, q, y, off.data());
     if (rc) return rc;
     const int P = 6 + p + q;
-    if (!lb || !ub) return fail(LDSR_EINVAL, "lb and ub must not be NULL");
-    for (int c = 0; c < P; c++) {
-        if (!std::isfinite(lb[c]) || !std::isfinite(ub[c]) || !std::isfinite(ub[c] - lb[c]))
-            return fail(LDSR_EINVAL, "lb and ub must be finite");
-        if (lb[c] > ub[c]) return fail(LDSR_EINVAL, "lb must be <= ub in every gene");
-    }
+    rc = check_box(lb, ub, P, "gene");
+    if (rc) return rc;
     if (!std::isfinite(lambda)) return fail(LDSR_EINVAL, "lambda must be finite");
     if (n_suggestions < 0 || n_suggestions > n)
         return fail(LDSR_EINVAL, "n_suggestions must be in 0 .. pop_per_island");
@@ -1593,14 +1656,14 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
     if (!theta_best || !pl_best || !n_gen) return fail(LDSR_EINVAL, "theta_best, pl_best and n_gen must not be NULL");
 
     const int n_cells = n_series * K * n;
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
-    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
     IntrScope intr_scope;
     ArenaLease lease;
     rc = arena_acquire(device, &lease.a);
     if (rc) return rc;
     Arena *A = lease.a;
+    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
     const WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_cells, LDSR_ALGO_SCAN, 1);
+    SeriesUpload U{n_series, T, p, q, y, u, v, shared_uv};
     // The scan kernel whitens the inputs by Svv / Tuu and has no answer for a series where one of them is
     // singular (fewer observations than columns of v, say), but Kalman_smoother does not need them: the
     // cells of such a series take the serial smoother, whatever else shares the call.  series_prep finds
@@ -1609,16 +1672,14 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
     const size_t cells_per_problem = (size_t)K * n;
     std::vector<char> singular((size_t)n_series, 0);
     int n_sing = 0;
-    size_t o_y = 0, o_u = 0, o_v = 0, o_lb = 0, o_ub = 0, o_sg = 0, in_bytes = 0, o_st = 0, o_bt = 0, o_tr = 0,
-           out_bytes = 0, o_pop0 = 0, o_pop1 = 0, o_fit = 0, o_lik = 0, o_cst = 0, o_soc = 0, o_X = 0, o_V = 0, o_ws = 0;
+    size_t o_lb = 0, o_ub = 0, o_sg = 0, in_bytes = 0, o_st = 0, o_bt = 0, o_tr = 0, out_bytes = 0, o_pop0 = 0,
+           o_pop1 = 0, o_fit = 0, o_lik = 0, o_cst = 0, o_soc = 0, o_X = 0, o_V = 0, o_ws = 0;
     const size_t pop_bytes = sizeof(double) * (size_t)n_cells * P;
-    char *dev = nullptr, *pin = nullptr, *ws = nullptr;
+    char *dev = nullptr, *pin = nullptr;
     for (int pass = 0;; pass++) {
         const size_t strip_cells = all_serial ? (size_t)n_cells : (size_t)n_sing * cells_per_problem;
         Carver c;
-        o_y = c.take(sizeof(double) * (size_t)n_series * T);
-        o_u = c.take(u ? sizeof(double) * nuv * T * p : 0);
-        o_v = c.take(v ? sizeof(double) * nuv * T * q : 0);
+        U.carve(c);
         o_lb = c.take(sizeof(double) * (size_t)P);
         o_ub = c.take(sizeof(double) * (size_t)P);
         o_sg = c.take(sizeof(double) * (size_t)n_series * n_suggestions * P);
@@ -1640,22 +1701,16 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
         rc = arena_reserve(A, c.o, in_bytes + align256(out_bytes) + sc_bytes);
         if (rc) return rc;
         dev = A->dev; pin = A->pin;
-        memcpy(pin + o_y, y, sizeof(double) * (size_t)n_series * T);
-        if (u) memcpy(pin + o_u, u, sizeof(double) * nuv * T * p);
-        if (v) memcpy(pin + o_v, v, sizeof(double) * nuv * T * q);
+        U.stage(A);
         memcpy(pin + o_lb, lb, sizeof(double) * (size_t)P);
         memcpy(pin + o_ub, ub, sizeof(double) * (size_t)P);
         if (n_suggestions) memcpy(pin + o_sg, suggestions, sizeof(double) * (size_t)n_series * n_suggestions * P);
         HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
-        ws = dev + o_ws;
-        HIPCHK(launch_series_prep(prep_params(n_series, T, p, q, PP, QQ, (const double *)(dev + o_y),
-                                              u ? (const double *)(dev + o_u) : nullptr,
-                                              v ? (const double *)(dev + o_v) : nullptr, shared_uv, ws, L, true),
-                                  n_series, A->stream));
+        HIPCHK(U.prep(device, A->stream, dev + o_ws, &L));
         if (all_serial || pass == 1) break;
         static_assert(offsetof(SeriesConst, status) == sizeof(int), "the copy below takes n_obs and status");
         int *h_sc = (int *)(pin + in_bytes + align256(out_bytes));
-        HIPCHK(hipMemcpy2DAsync(h_sc, 2 * sizeof(int), ws + L.sc, sizeof(SeriesConst), 2 * sizeof(int),
+        HIPCHK(hipMemcpy2DAsync(h_sc, 2 * sizeof(int), U.ps.ws + L.sc, sizeof(SeriesConst), 2 * sizeof(int),
                                 (size_t)n_series, hipMemcpyDeviceToHost, A->stream));
         HIPCHK(wait_stream(A->stream));
         for (int s = 0; s < n_series; s++)
@@ -1665,29 +1720,27 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
     std::vector<int> soc((size_t)n_cells);
     for (int cc = 0; cc < n_cells; cc++) soc[(size_t)cc] = cc / (K * n);
     SmootherTables tb;
-    rc = smoother_tables(device, A->stream, T, PP, QQ, ws, L, n_cells, soc, 0, (int *)(dev + o_soc), &tb, &singular);
+    rc = smoother_tables(U.ps, n_cells, soc.data(), 0, (int *)(dev + o_soc), &tb, &singular);
     if (rc) return rc;
     if (n_sing) {       // (the serial smoother's cell -> series map, which the scan launch's table replaces)
         rc = stage_h2d_async(device, A->stream, dev + o_soc, soc.data(), sizeof(int) * (size_t)n_cells);
         if (rc) return rc;
     }
-    SmootherTables tb_serial;       // (scan = false)
+    // (pen: only the scalars leave the kernel, and the strip X / V stands in for Y / J)
+    FitOut fo;
+    fo.X = fo.Y = (double *)(dev + o_X); fo.V = fo.J = (double *)(dev + o_V);
+    fo.lik = (double *)(dev + o_lik); fo.pen = (double *)(dev + o_fit); fo.status = (int *)(dev + o_cst);
+    const int *d_soc = (const int *)(dev + o_soc);
     // one generation's fitness: the scan launch (or the serial one) over all cells, then the singular series
     auto enqueue_fitness = [&](const double *d_pop) -> int {
-        int r = smoother_enqueue(A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv, ws, L,
-                                 n_cells, tb, d_pop, 0, 0, lambda, (double *)(dev + o_X), (double *)(dev + o_X),
-                                 (double *)(dev + o_V), (double *)(dev + o_V), (double *)(dev + o_lik),
-                                 (double *)(dev + o_fit), (int *)(dev + o_cst), (const int *)(dev + o_soc), true);
+        int r = smoother_enqueue(U.ps, n_cells, tb, d_soc, d_pop, 0, 0, lambda, fo);
         for (int s = 0, j = 0; s < n_series && !r && n_sing; s++) {
             if (!singular[(size_t)s]) continue;
-            const size_t c0 = (size_t)s * cells_per_problem;
-            double *X = (double *)(dev + o_X) + (size_t)j * cells_per_problem * T;
-            double *V = (double *)(dev + o_V) + (size_t)j * cells_per_problem * T;
-            r = smoother_enqueue(A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv, ws, L,
-                                 (int)cells_per_problem, tb_serial, d_pop + c0 * P, 0, 0, lambda, X, X, V, V,
-                                 (double *)(dev + o_lik) + c0, (double *)(dev + o_fit) + c0,
-                                 (int *)(dev + o_cst) + c0, (const int *)(dev + o_soc) + c0, true);
-            j++;
+            const size_t c0 = (size_t)s * cells_per_problem, t0 = (size_t)j++ * cells_per_problem * T;
+            FitOut f = fo;
+            f.X = f.Y = fo.X + t0; f.V = f.J = fo.V + t0;
+            f.lik += c0; f.pen += c0; f.status += c0;
+            r = smoother_enqueue(U.ps, (int)cells_per_problem, SmootherTables(), d_soc + c0, d_pop + c0 * P, 0, 0, lambda, f);
         }
         return r;
     };
@@ -1749,45 +1802,14 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
 }
 
 // ---- LDS_BFGS: ssqTrain, its gradient and the L-BFGS learner (bfgs.hip) ----------------------------
-// What both entries upload: the raw series (the kernels read the ABI's time-major u, v as they are and
-// find the missing y_t themselves), the cell -> series map and the cells' thetas.
-struct SsqUpload {
-    size_t o_y, o_u, o_v, o_soc, o_th;
-};
-static SsqUpload ssq_carve(Carver &c, int n_series, int T, int p, int q, const double *u, const double *v,
-                           int shared_uv, int n_cells) {
-    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
-    SsqUpload U;
-    U.o_y = c.take(sizeof(double) * (size_t)n_series * T);
-    U.o_u = c.take(u ? sizeof(double) * nuv * T * p : 0);
-    U.o_v = c.take(v ? sizeof(double) * nuv * T * q : 0);
-    U.o_soc = c.take(sizeof(int) * (size_t)n_cells);
-    U.o_th = c.take(sizeof(double) * (size_t)n_cells * (6 + p + q));
-    return U;
-}
-static void ssq_stage(const SsqUpload &U, char *pin, int n_series, int T, int p, int q, const double *y,
-                      const double *u, const double *v, int shared_uv, const int *cell_offsets,
-                      const double *theta) {
-    const size_t nuv = shared_uv ? 1 : (size_t)n_series;
-    memcpy(pin + U.o_y, y, sizeof(double) * (size_t)n_series * T);
-    if (u) memcpy(pin + U.o_u, u, sizeof(double) * nuv * T * p);
-    if (v) memcpy(pin + U.o_v, v, sizeof(double) * nuv * T * q);
-    int *soc = (int *)(pin + U.o_soc);
-    for (int s = 0; s < n_series; s++)
-        for (int cc = cell_offsets[s]; cc < cell_offsets[s + 1]; cc++) soc[cc] = s;
-    memcpy(pin + U.o_th, theta, sizeof(double) * (size_t)cell_offsets[n_series] * (6 + p + q));
-}
-static SsqSeries ssq_series(const SsqUpload &U, char *dev, int T, int p, int q, const double *u, const double *v,
-                            int shared_uv, int n_cells, double *d_strip) {
+// Both entries upload the raw series (the kernels read the ABI's time-major u, v as they are and find the
+// missing y_t themselves), the cell -> series map and the cells' thetas: a SeriesUpload with its cells.
+static SsqSeries ssq_series(const SeriesUpload &U, double *d_strip) {
     SsqSeries S;
-    S.n_cells = n_cells; S.T = T; S.p = p; S.q = q;
-    S.y = (const double *)(dev + U.o_y);
-    S.u = u ? (const double *)(dev + U.o_u) : nullptr;
-    S.v = v ? (const double *)(dev + U.o_v) : nullptr;
-    S.u_stride = shared_uv ? 0 : (long)T * p;
-    S.v_stride = shared_uv ? 0 : (long)T * q;
-    S.series_of_cell = (const int *)(dev + U.o_soc);
-    S.strip = d_strip;
+    S.n_cells = U.cell_offsets[U.n_series]; S.T = U.T; S.p = U.p; S.q = U.q;
+    S.y = U.d_y; S.u = U.d_u; S.v = U.d_v;
+    S.u_stride = U.shared_uv ? 0 : (long)U.T * U.p; S.v_stride = U.shared_uv ? 0 : (long)U.T * U.q;
+    S.series_of_cell = U.d_soc; S.strip = d_strip;
     return S;
 }
 static size_t ssq_strip_bytes(int n_cells, int T) {
@@ -1807,8 +1829,9 @@ extern "C" int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q
     rc = arena_acquire(device, &lease.a);
     if (rc) return rc;
     Arena *A = lease.a;
+    SeriesUpload U{n_series, T, p, q, y, u, v, shared_uv};
     Carver c;
-    const SsqUpload U = ssq_carve(c, n_series, T, p, q, u, v, shared_uv, n_cells);
+    U.carve(c, cell_offsets, theta);
     const size_t in_bytes = c.o;
     const size_t o_f = c.take(sizeof(double) * (size_t)n_cells);
     const size_t o_g = c.take(grad ? sizeof(double) * (size_t)n_cells * P : 0);
@@ -1818,11 +1841,11 @@ extern "C" int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q
     rc = arena_reserve(A, c.o, in_bytes + align256(out_bytes));
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
-    ssq_stage(U, pin, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta);
+    U.stage(A);
     HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
     SsqParams sp;
-    sp.S = ssq_series(U, dev, T, p, q, u, v, shared_uv, n_cells, strip_bytes ? (double *)(dev + o_strip) : nullptr);
-    sp.theta = (const double *)(dev + U.o_th);
+    sp.S = ssq_series(U, strip_bytes ? (double *)(dev + o_strip) : nullptr);
+    sp.theta = U.d_theta;
     sp.ssq = (double *)(dev + o_f);
     sp.grad = grad ? (double *)(dev + o_g) : nullptr;
     HIPCHK(launch_ssq_grad(sp, A->stream));
@@ -1846,12 +1869,8 @@ extern "C" int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, co
     int rc = check_common(n_series, T, p, q, y, cell_offsets);
     if (rc) return rc;
     const int P = 6 + p + q;
-    if (!lb || !ub) return fail(LDSR_EINVAL, "lb and ub must not be NULL");
-    for (int c = 0; c < P; c++) {
-        if (!std::isfinite(lb[c]) || !std::isfinite(ub[c]) || !std::isfinite(ub[c] - lb[c]))
-            return fail(LDSR_EINVAL, "lb and ub must be finite");
-        if (lb[c] > ub[c]) return fail(LDSR_EINVAL, "lb must be <= ub in every variable");
-    }
+    rc = check_box(lb, ub, P, "variable");
+    if (rc) return rc;
     if (maxit < 1) return fail(LDSR_EINVAL, "maxit must be >= 1");
     if (lmm < 1 || lmm > BFGS_MAX_LMM) return fail(LDSR_EINVAL, "lmm must be in 1 .. 8");
     if (!(factr >= 0.0) || !std::isfinite(factr)) return fail(LDSR_EINVAL, "factr must be finite and >= 0");
@@ -1860,17 +1879,17 @@ extern "C" int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, co
     if (!par0) return fail(LDSR_EINVAL, "par0 must not be NULL");
     if (!winner || !theta_w || !value_w) return fail(LDSR_EINVAL, "winner, theta_w and value_w must not be NULL");
     const int n_cells = cell_offsets[n_series];
-    const int PP = ldsr_pad_dim(p), QQ = ldsr_pad_dim(q);
     const bool want_fit = lik_w || X || Y || V || (J && fit_mode == 1);
     IntrScope intr_scope;
     ArenaLease lease;
     rc = arena_acquire(device, &lease.a);
     if (rc) return rc;
     Arena *A = lease.a;
-    const WsLayout L = ws_layout(n_series, T, PP, QQ, shared_uv, n_series, LDSR_ALGO_SCAN, 1);
+    const WsLayout L = ws_layout(n_series, T, ldsr_pad_dim(p), ldsr_pad_dim(q), shared_uv, n_series, LDSR_ALGO_SCAN, 1);
     const size_t nT = (size_t)n_series * T;
+    SeriesUpload U{n_series, T, p, q, y, u, v, shared_uv};
     Carver c;
-    const SsqUpload U = ssq_carve(c, n_series, T, p, q, u, v, shared_uv, n_cells);
+    U.carve(c, cell_offsets, par0);
     const size_t o_lb = c.take(sizeof(double) * (size_t)P);
     const size_t o_ub = c.take(sizeof(double) * (size_t)P);
     const size_t o_off = c.take(sizeof(int) * ((size_t)n_series + 1));
@@ -1902,15 +1921,15 @@ extern "C" int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, co
     rc = arena_reserve(A, c.o, in_bytes + align256(sel_bytes) + align256(std::max(cell_bytes, fit_bytes)));
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
-    ssq_stage(U, pin, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, par0);
+    U.stage(A);
     memcpy(pin + o_lb, lb, sizeof(double) * (size_t)P);
     memcpy(pin + o_ub, ub, sizeof(double) * (size_t)P);
     memcpy(pin + o_off, cell_offsets, sizeof(int) * ((size_t)n_series + 1));
     HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
 
     BfgsParams bp;
-    bp.S = ssq_series(U, dev, T, p, q, u, v, shared_uv, n_cells, strip_bytes ? (double *)(dev + o_strip) : nullptr);
-    bp.par0 = (const double *)(dev + U.o_th);
+    bp.S = ssq_series(U, strip_bytes ? (double *)(dev + o_strip) : nullptr);
+    bp.par0 = U.d_theta;
     bp.lb = (const double *)(dev + o_lb);
     bp.ub = (const double *)(dev + o_ub);
     bp.maxit = maxit; bp.lmm = lmm;
@@ -1962,17 +1981,13 @@ extern "C" int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, co
         if (fit_mode == 1) fill(J, nT);
     }
     if (n_w == 0) return LDSR_OK;
-    char *ws = dev + o_ws;
-    HIPCHK(launch_series_prep(prep_params(n_series, T, p, q, PP, QQ, (const double *)(dev + U.o_y),
-                                          u ? (const double *)(dev + U.o_u) : nullptr,
-                                          v ? (const double *)(dev + U.o_v) : nullptr, shared_uv, ws, L, true),
-                              n_series, A->stream));
+    HIPCHK(U.prep(device, A->stream, dev + o_ws, &L));
     rc = stage_h2d_async(device, A->stream, dev + o_fth, th.data(), sizeof(double) * (size_t)n_w * P);
     if (rc) return rc;
-    rc = launch_smoother(device, A->stream, T, p, q, PP, QQ, u != nullptr, v != nullptr, shared_uv, ws, L, n_w,
-                         ws_series, (const double *)(dev + o_fth), 1, fit_mode == 0 ? 1 : 0, 0.0,
-                         (double *)(dev + o_X), (double *)(dev + o_Y), (double *)(dev + o_V), (double *)(dev + o_J),
-                         (double *)(dev + o_lik), nullptr, (int *)(dev + o_fst), (int *)(dev + o_fsoc), false);
+    const FitOut fit{(double *)(dev + o_X), (double *)(dev + o_Y), (double *)(dev + o_V), (double *)(dev + o_J),
+                     (double *)(dev + o_lik), nullptr, (int *)(dev + o_fst)};
+    rc = launch_smoother(U.ps, n_w, ws_series.data(), (const double *)(dev + o_fth), 1, fit_mode == 0 ? 1 : 0, 0.0, fit,
+                         (int *)(dev + o_fsoc));
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(pbig, dev + o_lik, fit_bytes, hipMemcpyDeviceToHost, A->stream));
     HIPCHK(wait_stream(A->stream));
@@ -1985,22 +2000,6 @@ extern "C" int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, co
         if (J && fit_mode == 1) memcpy(J + s * T, pbig + (o_J - o_lik) + row, sizeof(double) * (size_t)T);
     }
     return LDSR_OK;
-}
-
-extern "C" int ldsr_propagate_batch(int device, int n_series, int T, int p, int q, const double *y,
-                                    const double *u, const double *v, int shared_uv,
-                                    const int *cell_offsets, const double *theta, int stdlik,
-                                    double *X, double *Y, double *V, double *lik) {
-    return run_fit_kernel(1, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta,
-                          stdlik, X, Y, V, nullptr, lik, nullptr, nullptr);
-}
-
-extern "C" int ldsr_mstep_batch(int device, int n_series, int T, int p, int q, const double *y,
-                                const double *u, const double *v, int shared_uv,
-                                const int *cell_offsets, const double *X, const double *V,
-                                const double *J, double *theta, int *status) {
-    return run_fit_kernel(2, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, nullptr,
-                          1, (double *)X, nullptr, (double *)V, (double *)J, nullptr, theta, status);
 }
 
 // R/LDS_reconstruction.R:50-58: best lik among models with C > 0 (NaN ignored); if no

@@ -121,6 +121,58 @@ def test_argument_validation_without_gpu():
     assert L.ldsr_em_workspace_bytes(1, 5000, 1, 2, 64, 2) > 0      # four waves per cell
     assert L.ldsr_em_workspace_bytes(1, 9000, 1, 2, 64, 2) == 0     # scan kernel: T <= 8192
     assert L.ldsr_em_workspace_bytes(1, 9000, 1, 2, 64, 0) > 0      # AUTO: serial kernel
+    # the learners' box: one check for both, each with its own noun (exact texts)
+    P, inf = 8, float("inf")
+    y4 = (C.c_double * 4)(0.1, -0.2, 0.3, 0.0)
+    par0 = (C.c_double * (2 * P))(*([0.5] * (2 * P)))
+    off2 = (C.c_int * 2)(0, 2)
+    th_w, val, win, ngen = (C.c_double * P)(), (C.c_double * 1)(), (C.c_int * 1)(), (C.c_int * 1)()
+
+    def box(base, i=None, x=0.0):
+        b = [base] * P
+        if i is not None:
+            b[i] = x
+        return (C.c_double * P)(*b)
+
+    def ga(lb, ub):
+        return L.ldsr_ga_batch(0, 1, 4, 1, 1, y4, None, None, 0, lb, ub, 1.0, 2, 8, 5, 3, 1, None, 0, th_w, val, ngen,
+                               None, None, None)
+
+    def bfgs(lb, ub):
+        return L.ldsr_bfgs_batch(0, 1, 4, 1, 1, y4, None, None, 0, off2, par0, lb, ub, 10, 5, 1e7, 0.0, 1, 0, None, None,
+                                 None, None, None, win, th_w, val, None, None, None, None, None)
+
+    for call, noun in ((ga, b"gene"), (bfgs, b"variable")):
+        for lb, ub, msg in ((None, box(0.9), b"lb and ub must not be NULL"),
+                            (box(0.1), None, b"lb and ub must not be NULL"),
+                            (box(0.1, 0, -inf), box(0.9), b"lb and ub must be finite"),
+                            (box(0.1), box(0.9, 7, float("nan")), b"lb and ub must be finite"),
+                            (box(0.1, 3, 0.95), box(0.9), b"lb must be <= ub in every " + noun),
+                            (box(0.1, 1, -1e308), box(0.9, 1, 1e308), b"lb and ub must be finite")):
+            assert call(lb, ub) == 1 and L.ldsr_last_error() == msg, (noun, L.ldsr_last_error())
+
+
+def test_cell_offsets_validation_without_gpu():
+    """The [S+1] cell offsets are checked once (api._offsets) for every entry that takes them with a theta per
+    cell: same ValueError texts from em_batch, em_restart_grid, ssq_train and bfgs_batch, before the library is
+    called."""
+    from ldsr_amd import api, bfgs
+    T, n = 6, 4
+    Y = np.zeros((2, T))
+    th = np.full((n, 8), 0.5)
+    lb, ub = np.full(8, 0.1), np.full(8, 0.9)
+    entries = (lambda y, off: api.em_batch(y, None, None, th, cell_offsets=off, niter=5),
+               lambda y, off: api.em_restart_grid(y, None, None, th, cell_offsets=off, niter=5),
+               lambda y, off: bfgs.ssq_train(y, None, None, th, cell_offsets=off),
+               lambda y, off: bfgs.bfgs_batch(y, None, None, th, lb, ub, cell_offsets=off))
+    for f in entries:
+        for y, off, msg in ((Y, [0, n], "cell_offsets must have S+1 entries ending at n_cells"),          # wrong length
+                            (Y[0], [0, 2, n], "cell_offsets must have S+1 entries ending at n_cells"),
+                            (Y, [0, 2, n - 1], "cell_offsets must have S+1 entries ending at n_cells"),   # last entry != n
+                            (Y, None, "cell_offsets is required with several series")):
+            with pytest.raises(ValueError) as e:
+                f(y, off)
+            assert str(e.value) == msg
 
 
 def test_launch_plan_of_every_shape():

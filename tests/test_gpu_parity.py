@@ -626,3 +626,102 @@ def test_long_wide_series_use_the_global_image_scan(eng, O, T, p, q, mask):
         r = eng.em_batch(y, u, v, th0, niter=niter, tol=tol, algo=2)
         ref = _oracle_batch(O, y, u, v, th0, niter, tol)
         _assert_batch_parity(r, ref, "GIMG T=%d p=%d q=%d" % (T, p, q))
+
+
+# ---- the pointer plumbing of the smoother-family, ssq and M-step host entries --------------------------
+def _plumbing_inputs():
+    """S = 2 series, T = 12, no u (p = 1), an own v per series (q = 3, so shared_uv = 0), two missing y in
+    series 1; five thetas that differ in every entry.  The smallest shape at which a transposed or mis-offset
+    pointer of the entries' upload (y | u | v | map | theta) or of their outputs still shows."""
+    from ldsr_amd import synth
+    rng = np.random.default_rng(20261018)
+    S, T, q = 2, 12, 3
+    Y = rng.normal(size=(S, T))
+    Y[1, [4, 9]] = np.nan
+    V = rng.normal(size=(S, q, T))
+    th = synth.make_init_packed(1, q, 5, seed=17)     # [A, B, C, D(3), Q, R, mu1, V1]
+    th[:, 6] = 0.3 + th[:, 0]
+    th[:, 7] = 0.05 + 0.5 * th[:, 2]
+    th[:, 8] = th[:, 1]
+    th[:, 9] = 0.5 + th[:, 0]
+    return Y, V, th
+
+
+@pytest.fixture(scope="module")
+def plumbing(O):
+    """The inputs and, for each theta on each series, what the oracle (and tests/bfgs_model.py for the
+    gradient) says: ref[s][i] for theta i on series s."""
+    import bfgs_model as M
+    Y, V, th = _plumbing_inputs()
+    lam = 0.7
+    ref = []
+    for s in range(2):
+        rows = []
+        for t in th:
+            ks, ks0 = O.kalman_smoother(Y[s], None, V[s], t), O.kalman_smoother(Y[s], None, V[s], t, stdlik=False)
+            pr = O.propagate(t, None, V[s], Y[s])
+            X = ks0["X"]
+            f, g = M.ssq_grad(t, Y[s], None, V[s])
+            rows.append({"smooth": ks, "propagate": pr, "ssq": np.nansum((Y[s] - pr["Y"]) ** 2), "grad": g,
+                         "pen": ks0["lik"] - lam * np.sum((X[1:] - t[0] * X[:-1]) ** 2)})
+            assert parity_close(f, rows[-1]["ssq"])
+            for r in (ks, pr):
+                assert all(np.all(np.isfinite(r[k])) for k in r)
+            assert np.isfinite(rows[-1]["pen"]) and np.all(np.isfinite(g))
+        ref.append(rows)
+    return {"Y": Y, "V": V, "th": th, "lam": lam, "ref": ref}
+
+
+def _assert_plumbing(eng, c, Y, V, off, series_of_cell):
+    """every entry on (Y, V) with c's thetas split by `off`, every cell against the oracle's row for its series"""
+    th, lam = c["th"], c["lam"]
+    sm = eng.smooth_batch(Y, None, V, th, cell_offsets=off)
+    pr = eng.smooth_batch(Y, None, V, th, cell_offsets=off, mode="propagate")
+    pen = eng.penalized_likelihood(Y, None, V, th, lam, cell_offsets=off)
+    f, g = eng.ssq_train(Y, None, V, th, cell_offsets=off, grad=True)
+    for i, s in enumerate(series_of_cell):
+        r = c["ref"][s][i]
+        for k in ("X", "Y", "V", "J", "lik"):
+            assert parity_close(sm[k][i], r["smooth"][k], RTOL, ATOL), ("smooth", k, i)
+        for k in ("X", "Y", "V", "lik"):
+            assert parity_close(pr[k][i], r["propagate"][k], RTOL, ATOL), ("propagate", k, i)
+        assert parity_close(pen[i], r["pen"], RTOL, ATOL), ("pen", i)
+        assert parity_close(f[i], r["ssq"], RTOL, ATOL), ("ssq", i)
+        assert parity_close(g[i], r["grad"], RTOL, ATOL), ("grad", i)
+    return sm, pr, pen, f, g
+
+
+def test_host_entry_pointer_plumbing(eng, O, plumbing):
+    """smooth_batch (both modes), penalized_likelihood, ssq_train with its gradient and Mstep through the
+    shared series upload: cell_offsets = [0, 3, 5], every cell compared."""
+    c = plumbing
+    sm = _assert_plumbing(eng, c, c["Y"], c["V"], [0, 3, 5], [0, 0, 0, 1, 1])[0]
+    fit = {k: sm[k][3] for k in "XVJ"}                 # series 1, theta 3
+    th1 = eng.pack_theta(eng.Mstep(c["Y"][1], None, c["V"][1], fit), 1, 3)
+    ref1 = O.mstep(c["Y"][1], None, c["V"][1], c["ref"][1][3]["smooth"])
+    assert np.all(np.isfinite(ref1))
+    assert parity_close(th1, ref1, RTOL, ATOL)
+    # the M-step entry itself on both series with the same split (Mstep only ever sends one series, one cell)
+    from ldsr_amd import _lib, api
+    Yc, _, Vc, S, T, p, q, shared = api._series(c["Y"], None, c["V"])
+    th, st = np.empty((5, 6 + p + q)), np.empty(5, dtype=np.int32)
+    _lib.check(_lib.lib().ldsr_mstep_batch(0, S, T, p, q, api._d(Yc), None, api._d(Vc), shared,
+                                           api._i(np.array([0, 3, 5], dtype=np.int32)), api._d(sm["X"]),
+                                           api._d(sm["V"]), api._d(sm["J"]), api._d(th), api._i(st)))
+    for i, s in enumerate([0, 0, 0, 1, 1]):
+        ref = O.mstep(c["Y"][s], None, c["V"][s], c["ref"][s][i]["smooth"])
+        assert np.all(np.isfinite(ref)) and st[i] == 0, ("mstep", i)
+        assert parity_close(th[i], ref, RTOL, ATOL), ("mstep", i)
+
+
+def test_host_entry_pointer_plumbing_series_without_cells(eng, plumbing):
+    """cell_offsets = [0, 0, 5]: series 0 has no cells; series 1's cells come out as from a call with that
+    series alone."""
+    c = plumbing
+    both = _assert_plumbing(eng, c, c["Y"], c["V"], [0, 0, 5], [1] * 5)
+    alone = _assert_plumbing(eng, c, c["Y"][1], c["V"][1], [0, 5], [1] * 5)
+    for name, a, b in zip(("smooth", "propagate"), both[:2], alone[:2]):
+        for k in a:
+            assert np.array_equal(a[k], b[k]), (name, k)
+    for name, a, b in zip(("pen", "ssq", "grad"), both[2:], alone[2:]):
+        assert np.array_equal(a, b), name
