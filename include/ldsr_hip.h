@@ -35,6 +35,8 @@
  *                            R/LDS_GA.R:174 and the winner's propagate / Kalman_smoother fit in ONE call.
  *                            This project's own L-BFGS, NOT the iterates of the
  *                            L-BFGS-B code behind stats::optim
+ *   ldsr_bfgs_update_batch   LDS_BFGS_with_update (R/LDS_GA.R:90-127): the same L-BFGS on -penalized_likelihood
+ *   ldsr_pl_grad_batch       penalized_likelihood (R/LDS_GA.R:28-44) and its exact gradient for a batch of thetas
  *   ldsr_ssq_grad_batch      ssqTrain (R/LDS_GA.R:143-147) and its exact gradient for a batch of thetas
  *   ldsr_select_restart      the argmax-with-C>0 rule of R/LDS_reconstruction.R:50-58
  *   ldsr_simulate_batch      LDS_rep / one_LDS_rep (R/stochastics.R:18-63): num_reps stochastic
@@ -86,6 +88,7 @@ extern "C" {
 #define LDSR_EUNSUPPORTED 2  /* p or q above the compiled limit */
 #define LDSR_EHIP 3          /* a HIP runtime call failed (no device, OOM, launch error) */
 #define LDSR_EINTERRUPTED 4  /* the interrupt callback asked to stop; outputs are incomplete */
+#define LDSR_EINTERNAL 5     /* the library's own pre-launch check refused a launch; nothing ran */
 
 /* per-cell status words */
 #define LDSR_CELL_OK 0
@@ -225,7 +228,9 @@ size_t ldsr_kernel_inventory(char *buf, size_t len);
 int ldsr_last_em_kernel(int device, char *buf, size_t len);
 
 /* Batched Kalman_smoother: one E-step for each cell's theta.  Host pointers.
- * X, Y, V, J: [n_cells][T] (any may be NULL); lik: [n_cells].  stdlik as src/EM.cpp:124. */
+ * X, Y, V, J: [n_cells][T] (any may be NULL); lik: [n_cells].  stdlik as src/EM.cpp:124.
+ * A series whose Svv / Tuu is singular (an EM call flags it LDSR_CELL_SINGULAR) has a smoother all the same:
+ * this entry and ldsr_penalized_lik_batch run its cells on the serial kernel. */
 int ldsr_smooth_batch(int device, int n_series, int T, int p, int q, const double *y,
                       const double *u, const double *v, int shared_uv,
                       const int *cell_offsets, const double *theta, int stdlik, double *X,
@@ -329,6 +334,38 @@ int ldsr_bfgs_batch(int device, int n_series, int T, int p, int q, const double 
                     int select_max, int fit_mode, double *par_all, double *value_all, int *n_iter_all,
                     int *n_eval_all, int *status_all, int *winner, double *theta_w, double *value_w,
                     double *lik_w, double *X, double *Y, double *V, double *J);
+
+/* penalized_likelihood (R/LDS_GA.R:28-44) and its gradient: pl = lik - lambda ssq with lik the likelihood of
+ * Kalman_smoother (stdlik = FALSE) and ssq = sum (Xs_{t+1} - A Xs_t - B u_t)^2 over the smoothed means; grad =
+ * d pl / d theta in all of A, B, C, D, Q, R, mu1, V1 by reverse mode over the smoother:
+ * exact, five passes over the series, each a scan over the 64 lanes of the cell's wavefront.  pl is bit-identical
+ * with and without grad.  The slots of an absent input have gradient 0; NaN and +-Inf in y: missing.
+ *   pl [n_cells]   grad [n_cells][6+p+q], may be NULL (values only).  Host pointers; lambda finite.
+ * Before the launch the bytes the kernel will touch behind every device pointer are checked against the call's
+ * block; a mismatch returns LDSR_EINTERNAL with the pointer's name in ldsr_last_error() and launches nothing. */
+int ldsr_pl_grad_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                       const double *v, int shared_uv, const int *cell_offsets, const double *theta,
+                       double lambda, double *pl, double *grad);
+
+/* LDS_BFGS_with_update (R/LDS_GA.R:90-127): ldsr_bfgs_batch's optimiser, arguments and outputs with the
+ * objective f = -pl at the given lambda (finite).  value_all / value_w are the minimised -pl; a start with some
+ * S_t <= 0 is LDSR_BFGS_NONFINITE.  select_max != 0 is the reference's literal which.max(optim.vals)
+ * (R/LDS_GA.R:116), the LARGEST minimised value.  There is no fit_mode: the winners' fit is always
+ * Kalman_smoother(theta_w) with the standardised likelihood, J included.  The pre-launch check of
+ * ldsr_pl_grad_batch applies. */
+int ldsr_bfgs_update_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                           const double *v, int shared_uv, const int *cell_offsets, const double *par0,
+                           const double *lb, const double *ub, double lambda, int maxit, int lmm, double factr,
+                           double pgtol, int select_max, double *par_all, double *value_all, int *n_iter_all,
+                           int *n_eval_all, int *status_all, int *winner, double *theta_w, double *value_w,
+                           double *lik_w, double *X, double *Y, double *V, double *J);
+
+/* Test hook of that pre-launch check, no device needed: lays out the block of ldsr_pl_grad_batch (kernel = 0) or
+ * ldsr_bfgs_update_batch (kernel = 1) for the given shape at a made-up base address, reserves strip_short bytes
+ * less for the strip, moves grad (kernel 0) or par (kernel 1) up by out_shift bytes, and runs the check on the
+ * kernel's parameter struct.  -> LDSR_OK, or LDSR_EINTERNAL with the field's name in ldsr_last_error(). */
+int ldsr_plg_extent_check(int kernel, int n_series, int T, int p, int q, int has_u, int has_v, int shared_uv,
+                          const int *cell_offsets, int with_grad, long strip_short, long out_shift);
 
 /* Stochastic replicates: one_LDS_rep / LDS_rep (R/stochastics.R:18-63) for n_models thetas x
  * num_reps replicates of T steps,

@@ -8,5 +8,5 @@ from .api import (ALGO_AUTO, ALGO_PAIR, ALGO_QUAD, ALGO_SCAN, ALGO_SERIAL, Kalma
                   select_restart, smooth_batch, unpack_theta)
 from .sim import LDS_rep, one_LDS_rep, simulate_batch  # noqa: F401,E402
 from .ga import LDS_GA, ga_batch  # noqa: F401,E402
-from .bfgs import LDS_BFGS, bfgs_batch, ssq_train  # noqa: F401,E402
+from .bfgs import LDS_BFGS, LDS_BFGS_with_update, bfgs_batch, bfgs_update_batch, pl_grad, ssq_train  # noqa: F401,E402
 from . import bfgs, cv, ga, shard, sim  # noqa: F401,E402

@@ -60,6 +60,13 @@ SIGNATURES = {
     "ldsr_bfgs_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _ip, _dp,
                                   _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                   _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ldsr_pl_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _ip,
+                                     _dp, C.c_double, _dp, _dp]),
+    "ldsr_bfgs_update_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _ip,
+                                         _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double,
+                                         C.c_int, _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ldsr_plg_extent_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        _ip, C.c_int, C.c_long, C.c_long]),
     "ldsr_simulate_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp,
                                       _dp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, _dp, _dp, _dp]),
     "ldsr_simulate_draw_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int,

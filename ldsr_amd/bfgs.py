@@ -6,7 +6,9 @@ Everything numeric runs on the GPU behind one library call (ldsr_bfgs_batch, inc
 persistent wavefront per restart runs the whole optimisation, the winner is picked on the device and only
 its model crosses PCIe.  The optimiser is this project's own specification ("The
 bound-constrained L-BFGS"); it does not reproduce the iterates of the L-BFGS-B code behind stats::optim.
-This module only marshals and draws the start points -- there is no host implementation of the objective
+LDS_BFGS_with_update (R/LDS_GA.R:90-127) is the same optimiser on f = -penalized_likelihood
+(ldsr_bfgs_update_batch; the objective and its exact gradient: pl_grad).
+This module only marshals and draws the start points -- there is no host implementation of the objectives
 or of the optimiser."""
 import numpy as np
 
@@ -33,15 +35,10 @@ def ssq_train(y, u, v, theta_packed, cell_offsets=None, grad=False, device=0):
     return (f, g) if grad else f
 
 
-def bfgs_batch(y, u, v, par0, lb, ub, cell_offsets=None, maxit=100, lmm=5, factr=1e7, pgtol=0.0,
-               select="reference", smooth=False, device=0, return_all=True):
-    """One L-BFGS run per row of par0 [n_cells, 6+p+q], all in one call.  y: [T], or [S, T] (the folds of
-    cvLDS with shared u, v) with cell_offsets [S+1].  select: "reference" is the reference's literal
-    which.max(optim.vals) (R/LDS_GA.R:174: the LARGEST of the minimised values), "min" the smallest.
-
-    Returns dict: winner [S] (global cell index, -1 = none), theta [S, P], value [S], lik [S],
-    X / Y / V [S, T] (J too with smooth=True: the fit is Kalman_smoother's, else propagate's); plus
-    "all" (per-cell par, value, n_iter, n_eval, status) when return_all."""
+def _bfgs_call(entry, lam, y, u, v, par0, lb, ub, cell_offsets, maxit, lmm, factr, pgtol, select, with_J, fit_mode,
+               device, return_all):
+    """bfgs_batch / bfgs_update_batch: marshal, call `entry` (lam, fit_mode: the arguments only one of the two
+    takes, None where it takes none) and shape the result"""
     if select not in ("reference", "min"):
         raise ValueError('select must be "reference" or "min"')
     Y, U, V, S, T, p, q, shared = _series(y, u, v)
@@ -57,21 +54,63 @@ def bfgs_batch(y, u, v, par0, lb, ub, cell_offsets=None, maxit=100, lmm=5, factr
     off = _offsets(cell_offsets, S, n)
     out = {"winner": np.empty(S, dtype=np.int32), "theta": np.empty((S, P)), "value": np.empty(S),
            "lik": np.empty(S), "X": np.empty((S, T)), "Y": np.empty((S, T)), "V": np.empty((S, T))}
-    if smooth:
+    if with_J:
         out["J"] = np.empty((S, T))
     a = {}
     if return_all:
         a = {"par": np.empty((n, P)), "value": np.empty(n), "n_iter": np.empty(n, dtype=np.int32),
              "n_eval": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.int32)}
-    _lib.check(_lib.lib().ldsr_bfgs_batch(
-        device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off), _d(par0), _d(lb), _d(ub), int(maxit),
-        int(lmm), float(factr), float(pgtol), int(select == "reference"), int(bool(smooth)),
+    _lib.check(getattr(_lib.lib(), entry)(
+        device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off), _d(par0), _d(lb), _d(ub),
+        *([] if lam is None else [float(lam)]), int(maxit), int(lmm), float(factr), float(pgtol),
+        int(select == "reference"), *([] if fit_mode is None else [int(fit_mode)]),
         _d(a.get("par")), _d(a.get("value")), _i(a.get("n_iter")), _i(a.get("n_eval")), _i(a.get("status")),
         _i(out["winner"]), _d(out["theta"]), _d(out["value"]), _d(out["lik"]), _d(out["X"]), _d(out["Y"]),
         _d(out["V"]), _d(out.get("J"))))
     if return_all:
         out["all"] = a
     return out
+
+
+def bfgs_batch(y, u, v, par0, lb, ub, cell_offsets=None, maxit=100, lmm=5, factr=1e7, pgtol=0.0,
+               select="reference", smooth=False, device=0, return_all=True):
+    """One L-BFGS run per row of par0 [n_cells, 6+p+q], all in one call.  y: [T], or [S, T] (the folds of
+    cvLDS with shared u, v) with cell_offsets [S+1].  select: "reference" is the reference's literal
+    which.max(optim.vals) (R/LDS_GA.R:174: the LARGEST of the minimised values), "min" the smallest.
+
+    Returns dict: winner [S] (global cell index, -1 = none), theta [S, P], value [S], lik [S],
+    X / Y / V [S, T] (J too with smooth=True: the fit is Kalman_smoother's, else propagate's); plus
+    "all" (per-cell par, value, n_iter, n_eval, status) when return_all."""
+    return _bfgs_call("ldsr_bfgs_batch", None, y, u, v, par0, lb, ub, cell_offsets, maxit, lmm, factr, pgtol, select,
+                      bool(smooth), bool(smooth), device, return_all)
+
+
+def pl_grad(y, u, v, theta_packed, lam, cell_offsets=None, grad=False, device=0):
+    """penalized_likelihood (R/LDS_GA.R:28-44) for a batch of packed thetas [n, 6+p+q]: lik(stdlik=FALSE) -
+    lam * ssq, one wavefront per theta.  With grad=True -> (pl [n], d pl / d theta [n, 6+p+q])."""
+    Y, U, V, S, T, p, q, shared = _series(y, u, v)
+    theta = np.ascontiguousarray(np.atleast_2d(theta_packed), dtype=np.float64)
+    if theta.shape[1] != 6 + p + q:
+        raise ValueError("theta must be [n, %d]" % (6 + p + q))
+    n = theta.shape[0]
+    off = _offsets(cell_offsets, S, n)
+    f = np.empty(n)
+    g = np.empty_like(theta) if grad else None
+    _lib.check(_lib.lib().ldsr_pl_grad_batch(device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off), _d(theta),
+                                             float(lam), _d(f), _d(g)))
+    return (f, g) if grad else f
+
+
+def bfgs_update_batch(y, u, v, par0, lb, ub, lam=1.0, cell_offsets=None, maxit=100, lmm=5, factr=1e7, pgtol=0.0,
+                      select="reference", device=0, return_all=True):
+    """bfgs_batch on f = -penalized_likelihood at lam: one L-BFGS run per row of par0 [n_cells, 6+p+q].
+    select: "reference" is the reference's literal which.max(optim.vals) (R/LDS_GA.R:116: the LARGEST of the
+    minimised values), "min" the smallest.
+
+    Returns dict: winner [S], theta [S, P], value [S] (the minimised -pl), lik [S], X / Y / V / J [S, T] (the
+    fit is Kalman_smoother's); plus "all" (per-cell par, value, n_iter, n_eval, status) when return_all."""
+    return _bfgs_call("ldsr_bfgs_update_batch", lam, y, u, v, par0, lb, ub, cell_offsets, maxit, lmm, factr, pgtol,
+                      select, True, None, device, return_all)
 
 
 def start_points(lb, ub, num_restarts, seed=None, r_seed=None, first=0):
@@ -120,5 +159,27 @@ def LDS_BFGS(y, u, v, ub=None, lb=None, num_restarts=100, seed=None, r_seed=None
     if smooth:
         fit["J"] = r["J"][0:1].copy()
     fit["lik"] = float(r["lik"][0])
+    return {"theta": unpack_theta(r["theta"][0], p, q), "fit": fit, "lik": fit["lik"], "pl": float(r["value"][0]),
+            "all": dict(r["all"], selected=k, par0=par0)}
+
+
+def LDS_BFGS_with_update(y, u, v, lambda_=1.0, ub=None, lb=None, num_restarts=100, seed=None, r_seed=None,
+                         select="reference", maxit=100, device=0):
+    """-> {"theta", "fit", "lik", "pl", "all"}   (R/LDS_GA.R:118-126): theta as the reference's list, fit =
+    Kalman_smoother(y, u, v, theta) with the standardised likelihood, lik = fit's, pl = the selected restart's
+    minimised -penalized_likelihood; "all" = the per-restart par / value / n_iter / n_eval / status (+ selected,
+    par0)."""
+    if ub is None or lb is None:
+        raise ValueError("LDS_BFGS_with_update needs ub and lb")
+    p, q = _dims(u, v)
+    par0 = start_points(lb, ub, num_restarts, seed=seed, r_seed=r_seed)
+    r = bfgs_update_batch(y, u, v, par0, lb, ub, lam=lambda_, maxit=maxit, select=select, device=device)
+    if r["theta"].shape[0] != 1:
+        raise ValueError("LDS_BFGS_with_update takes one series; bfgs_update_batch runs several")
+    k = int(r["winner"][0])
+    if k < 0:
+        raise _lib.LdsrError("LDS_BFGS_with_update: no restart has a finite objective value")
+    fit = {"X": r["X"][0:1].copy(), "Y": r["Y"][0:1].copy(), "V": r["V"][0:1].copy(), "J": r["J"][0:1].copy(),
+           "lik": float(r["lik"][0])}
     return {"theta": unpack_theta(r["theta"][0], p, q), "fit": fit, "lik": fit["lik"], "pl": float(r["value"][0]),
             "all": dict(r["all"], selected=k, par0=par0)}

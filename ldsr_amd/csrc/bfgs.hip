@@ -22,8 +22,7 @@
 // Every product-sum is an explicit fma and contraction is off, so the forward pass gives the same f
 // with and without the gradient.
 #include "bfgs.h"
-#include "em_scan_impl.h"     // dppz / dppd, readlane_d, wave_sum_n
-#include "../../include/ldsr_hip.h"
+#include "bfgs_impl.h"        // the optimiser; em_scan_impl.h: dppz / dppd, readlane_d, wave_sum_n
 
 #pragma clang fp contract(off)
 
@@ -197,18 +196,6 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
     return f;
 }
 
-__device__ __forceinline__ double wave_sum1(double x) {
-    double a[1] = {x};
-    wave_sum_n<1>(a);
-    return a[0];
-}
-
-__device__ __forceinline__ double wave_max1(double x) {      // x >= 0 or NaN; NaN in any lane gives NaN
-    bool bad = x != x;
-    for (int d = 32; d >= 1; d >>= 1) x = fmax(x, __shfl_xor(x, d, 64));
-    return __any(bad) ? NAN : x;
-}
-
 __global__ __launch_bounds__(64) void ldsr_ssq_grad_kernel(SsqParams prm) {
     extern __shared__ double lds_strip[];
     const int lane = threadIdx.x;
@@ -224,7 +211,13 @@ __global__ __launch_bounds__(64) void ldsr_ssq_grad_kernel(SsqParams prm) {
     }
 }
 
-// The optimiser: INTEGRATION.md "The bound-constrained L-BFGS", step for step.
+struct SsqObjective {
+    SsqCell c;
+    template <bool GRAD>
+    __device__ __forceinline__ double eval(double x, int lane, double *g) const { return ssq_eval<GRAD>(c, x, lane, g); }
+};
+
+// The optimiser (bfgs_impl.h) on ssqTrain.
 __global__ __launch_bounds__(64) void ldsr_bfgs_kernel(BfgsParams prm) {
     extern __shared__ double lds_strip[];
     const int lane = threadIdx.x;
@@ -232,117 +225,8 @@ __global__ __launch_bounds__(64) void ldsr_bfgs_kernel(BfgsParams prm) {
     const bool mine = lane < P;
     const double lo = mine ? prm.lb[lane] : 0.0, hi = mine ? prm.ub[lane] : 0.0;
     for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
-        const SsqCell c = ssq_cell(prm.S, cell, lds_strip);
-        const double x_in = mine ? prm.par0[(size_t)cell * P + lane] : 0.0;
-        double x = fmin(fmax(x_in, lo), hi);
-        double g = 0.0;
-        double f = ssq_eval<true>(c, x, lane, &g);
-        int n_eval = 1, k = 0, status = LDSR_BFGS_MAXIT;
-        if (!isfinite(f)) {
-            if (mine) prm.par[(size_t)cell * P + lane] = x_in;
-            if (lane == 0) {
-                prm.value[cell] = NAN;
-                prm.n_iter[cell] = 0;
-                prm.n_eval[cell] = n_eval;
-                prm.status[cell] = LDSR_BFGS_NONFINITE;
-            }
-            continue;
-        }
-        double sh[BFGS_MAX_LMM], yh[BFGS_MAX_LMM];      // curvature pairs, newest first
-#pragma unroll
-        for (int j = 0; j < BFGS_MAX_LMM; j++) { sh[j] = 0.0; yh[j] = 0.0; }
-        int cnt = 0;
-        for (;;) {
-            // the active set and the projected gradient
-            const bool active = !mine || lo == hi || (x <= lo && g > 0.0) || (x >= hi && g < 0.0);
-            const double pg = active ? 0.0 : g;
-            const double pgn = wave_max1(fabs(pg));
-            if (pgn <= prm.pgtol) { status = LDSR_BFGS_CONVERGED; break; }
-            if (k >= prm.maxit) { status = LDSR_BFGS_MAXIT; break; }
-            if (prm.intr && (k & 7) == 0 && *(const volatile int *)prm.intr != 0) { status = LDSR_BFGS_INTERRUPTED; break; }
-
-            // the direction: two-loop recursion over the pairs restricted to the free variables
-            double d = -pg;
-            if (cnt > 0) {
-                double sy_yy[2 * BFGS_MAX_LMM];
-#pragma unroll
-                for (int j = 0; j < BFGS_MAX_LMM; j++) {
-                    const double sj = active ? 0.0 : sh[j], yj = active ? 0.0 : yh[j];
-                    sy_yy[2 * j] = sj * yj;
-                    sy_yy[2 * j + 1] = yj * yj;
-                }
-                wave_sum_n<2 * BFGS_MAX_LMM>(sy_yy);
-                double al[BFGS_MAX_LMM];
-                double qv = pg, gamma = 1.0;
-                bool have_gamma = false;
-#pragma unroll
-                for (int j = 0; j < BFGS_MAX_LMM; j++) {
-                    al[j] = 0.0;
-                    const double sy = sy_yy[2 * j], yy = sy_yy[2 * j + 1];
-                    if (j < cnt && sy > 2.2e-16 * yy) {
-                        al[j] = wave_sum1(active ? 0.0 : sh[j] * qv) / sy;
-                        if (!active) qv = fma(-al[j], yh[j], qv);
-                        if (!have_gamma) { gamma = sy / yy; have_gamma = true; }
-                    }
-                }
-                qv *= gamma;
-#pragma unroll
-                for (int j = BFGS_MAX_LMM - 1; j >= 0; j--) {
-                    const double sy = sy_yy[2 * j], yy = sy_yy[2 * j + 1];
-                    if (j < cnt && sy > 2.2e-16 * yy) {
-                        const double be = wave_sum1(active ? 0.0 : yh[j] * qv) / sy;
-                        if (!active) qv = fma(al[j] - be, sh[j], qv);
-                    }
-                }
-                d = active ? 0.0 : -qv;
-            }
-            double gd = wave_sum1(g * d);
-            if (cnt > 0 && !(gd < 0.0)) {       // not a descent direction: steepest descent, memory cleared
-                cnt = 0;
-                d = -pg;
-                gd = wave_sum1(g * d);
-            }
-
-            // projected backtracking
-            double alpha = k == 0 ? fmin(1.0, 1.0 / pgn) : 1.0;
-            double xt = x, ft = f;
-            bool ok = false;
-            for (int trial = 0; trial < BFGS_LS_TRIALS; trial++) {
-                xt = fmin(fmax(fma(alpha, d, x), lo), hi);
-                ft = ssq_eval<false>(c, xt, lane, nullptr);
-                n_eval++;
-                const double slope = wave_sum1(g * (xt - x));
-                if (isfinite(ft) && ft <= fma(1e-4, slope, f)) { ok = true; break; }
-                alpha *= 0.5;
-            }
-            if (!ok) { status = LDSR_BFGS_LINESEARCH; break; }
-
-            // the gradient at the accepted point, the new pair, the stop rule
-            double gt = 0.0;
-            ft = ssq_eval<true>(c, xt, lane, &gt);
-            n_eval++;
-            const double sv = xt - x, yv = gt - g;
-            double pr[2] = {sv * yv, yv * yv};
-            wave_sum_n<2>(pr);
-            if (pr[0] > 2.2e-16 * pr[1]) {
-#pragma unroll
-                for (int j = BFGS_MAX_LMM - 1; j > 0; j--) { sh[j] = sh[j - 1]; yh[j] = yh[j - 1]; }
-                sh[0] = sv;
-                yh[0] = yv;
-                cnt = min(cnt + 1, prm.lmm);
-            }
-            const double drop = (f - ft) / fmax(fmax(fabs(f), fabs(ft)), 1.0);
-            x = xt; f = ft; g = gt;
-            k++;
-            if (drop <= prm.ftol) { status = LDSR_BFGS_CONVERGED; break; }
-        }
-        if (mine) prm.par[(size_t)cell * P + lane] = x;
-        if (lane == 0) {
-            prm.value[cell] = f;
-            prm.n_iter[cell] = k;
-            prm.n_eval[cell] = n_eval;
-            prm.status[cell] = status;
-        }
+        const SsqObjective obj{ssq_cell(prm.S, cell, lds_strip)};
+        bfgs_cell(obj, prm, cell, P, lane, mine, lo, hi);
     }
 }
 

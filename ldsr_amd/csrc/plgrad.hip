@@ -1,0 +1,335 @@
+// plgrad.hip -- the penalised likelihood pl = lik - lambda ssq (R/LDS_GA.R:28-44) with its exact gradient on
+// the device, and the L-BFGS learner on f = -pl (LDS_BFGS_with_update, R/LDS_GA.R:90-127; the optimiser is
+// bfgs_impl.h, the specification INTEGRATION.md "The bound-constrained L-BFGS").
+//
+// One wave per (series, restart) cell, lane i holds variable i of theta.  The time recursions run over the
+// wave in chunks of 64 steps with a carry between chunks; every one of them is an inclusive scan of maps
+// under composition (DPP row shifts and broadcasts), affine maps for the means and the adjoints, 2 x 2
+// projective maps with an exact power-of-two renormalisation for the variance.  The passes:
+//   forward   Vp_t by the scan of the Riccati steps, then S_t, K_t, Vu_t of each lane's own step from its entry
+//             state with the reference's expressions; Xp_t by the affine scan with A (1 - K_t C); d_t, Xu_t,
+//             the likelihood terms, J_t and the source of Xs_t
+//   pass 3    backward: Xs_t = J_t Xs_{t+1} + (Xu_t - J_t Xp_{t+1}), e_t, ssq -- a value-only evaluation ends here
+//   pass 4    forward: a_t (adjoint of Xs_t), coefficient J_{t-1}; the adjoint of J_t
+//   pass 5    backward: xp_t, then vp_t whose source needs xu_t of the same step; the parameter gradients
+// What a later pass needs of a step lies in the wave's strip of the device workspace (plgrad.h).  The per-step
+// arithmetic and every address are plgrad.h's host/device functions; this file adds the cross-lane part.
+//
+// Every product-sum is an explicit fma and contraction is off: the value is the same with and without the
+// gradient.
+#include "plgrad.h"
+#include "bfgs_impl.h"        // the optimiser; em_scan_impl.h: dppd, readlane_d, wave_sum_n
+
+#pragma clang fp contract(off)
+
+#define MAXPQ LDSR_MAXPQ
+
+template <int CTRL, int RM>
+__device__ __forceinline__ PlgAff aff_from(const PlgAff &x) {       // identity where the DPP source does not exist
+    return PlgAff{dppd<CTRL, RM>(1.0, x.a), dppd<CTRL, RM>(0.0, x.b)};
+}
+// inclusive scan over the lanes: lane l gets (map of lane l) after ... after (map of lane 0)
+__device__ __forceinline__ PlgAff aff_scan(PlgAff x) {
+    x = plg_aff_then(aff_from<DPP_ROW_SHR(1), 0xF>(x), x);
+    x = plg_aff_then(aff_from<DPP_ROW_SHR(2), 0xF>(x), x);
+    x = plg_aff_then(aff_from<DPP_ROW_SHR(4), 0xF>(x), x);
+    x = plg_aff_then(aff_from<DPP_ROW_SHR(8), 0xF>(x), x);
+    x = plg_aff_then(aff_from<DPP_ROW_BCAST15, 0xA>(x), x);          // lane 15 -> row 1, lane 47 -> row 3
+    x = plg_aff_then(aff_from<DPP_ROW_BCAST31, 0xC>(x), x);          // lane 31 -> rows 2, 3
+    return x;
+}
+
+template <int CTRL, int RM>
+__device__ __forceinline__ PlgMob mob_from(const PlgMob &x) {
+    return PlgMob{dppd<CTRL, RM>(1.0, x.m00), dppd<CTRL, RM>(0.0, x.m01), dppd<CTRL, RM>(0.0, x.m10),
+                  dppd<CTRL, RM>(1.0, x.m11)};
+}
+__device__ __forceinline__ PlgMob mob_scan(PlgMob x) {
+    x = plg_mob_then(mob_from<DPP_ROW_SHR(1), 0xF>(x), x);
+    x = plg_mob_then(mob_from<DPP_ROW_SHR(2), 0xF>(x), x);
+    x = plg_mob_then(mob_from<DPP_ROW_SHR(4), 0xF>(x), x);
+    x = plg_mob_then(mob_from<DPP_ROW_SHR(8), 0xF>(x), x);
+    x = plg_mob_then(mob_from<DPP_ROW_BCAST15, 0xA>(x), x);
+    x = plg_mob_then(mob_from<DPP_ROW_BCAST31, 0xC>(x), x);
+    return x;
+}
+
+// the value of the lane below (the step before in a forward pass, the step above in a backward one); lane 0
+// gets the carry of the chunk before
+__device__ __forceinline__ double lane_below(double carry, double x) { return dppd<DPP_WAVE_SHR1, 0xF>(carry, x); }
+
+// a wave's strip is written by one lane and read by another in the next pass
+__device__ __forceinline__ void strip_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one wave's view of its cell
+struct PlgCell {
+    const double *y, *u, *v;      // the series' rows (u, v null: absent)
+    double *strip;                // the wave's [PLG_NSTRIP][T]
+    int T, p, q;
+    double lambda;
+};
+
+__device__ __forceinline__ PlgCell plg_cell(const PlgSeries &S, int cell, double lambda) {
+    const int s = S.series_of_cell[plg_row_at(cell, 0, 1)];
+    PlgCell c;
+    c.T = S.T; c.p = S.p; c.q = S.q; c.lambda = lambda;
+    c.y = S.y + plg_y_at(s, 0, S.T);
+    c.u = S.u ? S.u + plg_uv_at(s, S.u_stride, 0, S.p, 0) : nullptr;
+    c.v = S.v ? S.v + plg_uv_at(s, S.v_stride, 0, S.q, 0) : nullptr;
+    c.strip = S.strip + plg_wave_strip((int)blockIdx.x, S.T);
+    return c;
+}
+
+// pl at the theta whose variable i sits in lane i (xv); with GRAD also d pl / d theta, variable i in lane i
+// (0 in the lanes beyond P).  The value is the same in every lane.
+template <bool GRAD>
+__device__ __forceinline__ double pl_eval(const PlgCell &c, double xv, int lane, double *g_out) {
+    const int T = c.T, p = c.p, q = c.q;
+    const PlgCoef co = plg_coef(readlane_d(xv, 0), readlane_d(xv, 1 + p), readlane_d(xv, 2 + p + q),
+                                readlane_d(xv, 3 + p + q));
+    const double mu1 = readlane_d(xv, 4 + p + q), V1 = readlane_d(xv, 5 + p + q);
+    double *const st = c.strip;
+    const int n_chunks = plg_chunks(T);
+
+    // ---- forward: the filter ----
+    double lik_terms = 0.0;
+    {
+        double Bk[MAXPQ], Dk[MAXPQ];
+#pragma unroll
+        for (int k = 0; k < MAXPQ; k++) {
+            Bk[k] = (c.u && k < p) ? readlane_d(xv, 1 + k) : 0.0;
+            Dk[k] = (c.v && k < q) ? readlane_d(xv, 2 + p + k) : 0.0;
+        }
+        double carry_V = V1, carry_X = mu1;
+        for (int ch = 0; ch < n_chunks; ch++) {
+            const int t = plg_fwd_step(ch, lane);
+            const bool in = t < T;
+            double bu = 0.0, dv = 0.0, yt = NAN;
+            if (in) {
+                if (c.u) {
+#pragma unroll
+                    for (int k = 0; k < MAXPQ; k++)
+                        if (k < p) bu = fma(Bk[k], c.u[plg_uv_at(0, 0, t, p, k)], bu);
+                }
+                if (c.v) {
+#pragma unroll
+                    for (int k = 0; k < MAXPQ; k++)
+                        if (k < q) dv = fma(Dk[k], c.v[plg_uv_at(0, 0, t, q, k)], dv);
+                }
+                yt = c.y[plg_y_at(0, t, T)];
+            }
+            const bool obs = in && isfinite(yt);
+            const double ymdv = obs ? yt - dv : 0.0;
+            // the variance: Vp at the exit of every step, then each lane's own step from its entry state
+            const PlgMob m = mob_scan(in ? plg_mob_step(co, obs) : plg_mob_identity());
+            const double Vp_next = plg_mob_apply(m, carry_V);
+            const double Vp = lane_below(carry_V, Vp_next);
+            carry_V = readlane_d(Vp_next, 63);
+            double S, K, Vu;
+            plg_var_step(co, Vp, obs, &S, &K, &Vu);
+            // the mean
+            const PlgAff a = aff_scan(in ? plg_mean_step(co, K, ymdv, bu) : plg_aff_identity());
+            const double Xp_next = plg_aff_apply(a, carry_X);
+            const double Xp = lane_below(carry_X, Xp_next);
+            carry_X = readlane_d(Xp_next, 63);
+            const PlgFwd f = plg_fwd_step_values(co, Vp, Xp, obs, ymdv);
+            if (in) {
+                lik_terms += f.lik_term;
+                const PlgAff sm = plg_smooth_step(co, f.Vu, f.Xu, Vp_next, Xp_next, t == T - 1);
+                st[plg_strip_at(PLG_J, t, T)] = sm.a;
+                st[plg_strip_at(PLG_SRC, t, T)] = sm.b;
+                st[plg_strip_at(PLG_BU, t, T)] = bu;
+                if (GRAD) {
+                    st[plg_strip_at(PLG_VP, t, T)] = Vp;
+                    st[plg_strip_at(PLG_K, t, T)] = f.K;
+                    st[plg_strip_at(PLG_XP, t, T)] = Xp;
+                    st[plg_strip_at(PLG_D, t, T)] = f.d;
+                }
+            }
+        }
+    }
+    strip_sync();
+
+    // ---- pass 3, backward: the smoothed means and ssq ----
+    double ssq = 0.0;
+    {
+        double carry = 0.0;     // Xs of the step above the chunk (J = 0 at T - 1: never used there)
+        for (int ch = n_chunks - 1; ch >= 0; ch--) {
+            const int t = plg_rev_step(ch, lane);
+            const bool in = t < T;
+            PlgAff sm = plg_aff_identity();
+            double bu = 0.0;
+            if (in) {
+                sm.a = st[plg_strip_at(PLG_J, t, T)];
+                sm.b = st[plg_strip_at(PLG_SRC, t, T)];
+                bu = st[plg_strip_at(PLG_BU, t, T)];
+            }
+            const double Xs = plg_aff_apply(aff_scan(sm), carry);
+            const double Xs_next = lane_below(carry, Xs);
+            carry = readlane_d(Xs, 63);
+            if (in) {
+                const double e = plg_resid(co, Xs, Xs_next, bu, t == T - 1);
+                ssq = fma(e, e, ssq);
+                if (GRAD) {
+                    st[plg_strip_at(PLG_XS, t, T)] = Xs;
+                    st[plg_strip_at(PLG_EB, t, T)] = -2.0 * c.lambda * e;
+                }
+            }
+        }
+    }
+    double tot[2] = {lik_terms, ssq};
+    wave_sum_n<2>(tot);
+    const double pl = plg_value(tot[0], tot[1], c.lambda);
+    strip_sync();           // (the next evaluation's forward pass overwrites what other lanes have just read)
+    if (!GRAD) return pl;
+
+    // ---- pass 4, forward: the adjoints of Xs_t and J_t ----
+    {
+        double carry = 0.0;
+        for (int ch = 0; ch < n_chunks; ch++) {
+            const int t = plg_fwd_step(ch, lane);
+            const bool in = t < T;
+            PlgAff ad = plg_aff_identity();
+            if (in) {
+                const double eb = st[plg_strip_at(PLG_EB, t, T)];
+                const double J_prev = t > 0 ? st[plg_strip_at(PLG_J, t - 1, T)] : 0.0;
+                const double eb_prev = t > 0 ? st[plg_strip_at(PLG_EB, t - 1, T)] : 0.0;
+                ad = plg_adj_xs_step(co, J_prev, eb_prev, eb);
+            }
+            const double a = plg_aff_apply(aff_scan(ad), carry);
+            carry = readlane_d(a, 63);
+            if (in) {
+                const bool last = t == T - 1;
+                const double Xs_next = last ? 0.0 : st[plg_strip_at(PLG_XS, t + 1, T)];
+                const double Xp_next = last ? 0.0 : st[plg_strip_at(PLG_XP, t + 1, T)];
+                st[plg_strip_at(PLG_AB, t, T)] = a;
+                st[plg_strip_at(PLG_JB, t, T)] = plg_adj_j(a, Xs_next, Xp_next, last);
+            }
+        }
+    }
+    strip_sync();
+
+    // ---- pass 5, backward: the adjoints of Xp_t and Vp_t, the parameter gradients ----
+    double red[4 + 2 * MAXPQ];      // A, Q, C, R, B_k, D_k
+#pragma unroll
+    for (int k = 0; k < 4 + 2 * MAXPQ; k++) red[k] = 0.0;
+    double carry_xp = 0.0, carry_vp = 0.0;
+    for (int ch = n_chunks - 1; ch >= 0; ch--) {
+        const int t = plg_rev_step(ch, lane);
+        const bool in = t < T;
+        PlgBack b;
+        b.obs = false; b.first = t == 0; b.last = t >= T - 1;
+        b.Vp = 1.0; b.Vp_next = 1.0; b.K = 0.0; b.Xp = 0.0; b.d = 0.0; b.Xs = 0.0; b.eb = 0.0; b.a = 0.0; b.Jb = 0.0;
+        b.back = 0.0; b.back_v = 0.0;
+        if (in) {
+            b.obs = isfinite(c.y[plg_y_at(0, t, T)]);
+            b.Vp = st[plg_strip_at(PLG_VP, t, T)];
+            b.K = st[plg_strip_at(PLG_K, t, T)];
+            b.Xp = st[plg_strip_at(PLG_XP, t, T)];
+            b.d = st[plg_strip_at(PLG_D, t, T)];
+            b.Xs = st[plg_strip_at(PLG_XS, t, T)];
+            b.eb = st[plg_strip_at(PLG_EB, t, T)];
+            b.a = st[plg_strip_at(PLG_AB, t, T)];
+            if (!b.last) {
+                b.Vp_next = st[plg_strip_at(PLG_VP, t + 1, T)];
+                b.Jb = st[plg_strip_at(PLG_JB, t, T)];
+            }
+            if (!b.first) {
+                const double J_prev = st[plg_strip_at(PLG_J, t - 1, T)];
+                b.back = J_prev * st[plg_strip_at(PLG_AB, t - 1, T)];
+                b.back_v = st[plg_strip_at(PLG_JB, t - 1, T)] * J_prev / b.Vp;
+            }
+        }
+        plg_back_derive(co, &b);
+        const double xp = plg_aff_apply(aff_scan(in ? plg_adj_xp_step(co, b) : plg_aff_identity()), carry_xp);
+        const double xp_next = lane_below(carry_xp, xp);
+        carry_xp = readlane_d(xp, 63);
+        const double xu = plg_adj_xu(co, b, xp_next);
+        const double vp = plg_aff_apply(aff_scan(in ? plg_adj_vp_step(co, b, xu) : plg_aff_identity()), carry_vp);
+        const double vp_next = lane_below(carry_vp, vp);
+        carry_vp = readlane_d(vp, 63);
+        if (in) {
+            const PlgContrib g = plg_contrib(co, b, xu, plg_adj_vu(co, b, vp_next), xp_next, vp_next);
+            red[0] += g.gA; red[1] += g.gQ; red[2] += g.gC; red[3] += g.gR;
+            if (c.u) {
+#pragma unroll
+                for (int k = 0; k < MAXPQ; k++)
+                    if (k < p) red[4 + k] = fma(g.fB, c.u[plg_uv_at(0, 0, t, p, k)], red[4 + k]);
+            }
+            if (c.v) {
+#pragma unroll
+                for (int k = 0; k < MAXPQ; k++)
+                    if (k < q) red[4 + MAXPQ + k] = fma(g.fD, c.v[plg_uv_at(0, 0, t, q, k)], red[4 + MAXPQ + k]);
+            }
+        }
+    }
+    wave_sum_n<4 + 2 * MAXPQ>(red);
+    double g = 0.0;
+    if (lane == 0) g = red[0];
+    if (lane == 1 + p) g = red[2];
+    if (lane == 2 + p + q) g = red[1];
+    if (lane == 3 + p + q) g = red[3];
+    if (lane == 4 + p + q) g = carry_xp;       // d pl / d mu1 = xp_0
+    if (lane == 5 + p + q) g = carry_vp;       // d pl / d V1 = vp_0
+#pragma unroll
+    for (int k = 0; k < MAXPQ; k++) {
+        if (c.u && k < p && lane == 1 + k) g = red[4 + k];
+        if (c.v && k < q && lane == 2 + p + k) g = red[4 + MAXPQ + k];
+    }
+    strip_sync();
+    *g_out = g;
+    return pl;
+}
+
+__global__ __launch_bounds__(64) void ldsr_pl_grad_kernel(PlGradParams prm) {
+    const int lane = threadIdx.x;
+    const int P = 6 + prm.S.p + prm.S.q;
+    for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
+        const PlgCell c = plg_cell(prm.S, cell, prm.lambda);
+        const double xv = lane < P ? prm.theta[plg_row_at(cell, lane, P)] : 0.0;
+        double f, g = 0.0;
+        if (prm.grad) f = pl_eval<true>(c, xv, lane, &g);
+        else f = pl_eval<false>(c, xv, lane, nullptr);
+        if (lane == 0) prm.pl[plg_row_at(cell, 0, 1)] = f;
+        if (prm.grad && lane < P) prm.grad[plg_row_at(cell, lane, P)] = g;
+    }
+}
+
+// f = -pl
+struct NegPlObjective {
+    PlgCell c;
+    template <bool GRAD>
+    __device__ __forceinline__ double eval(double x, int lane, double *g) const {
+        double gp = 0.0;
+        const double f = -pl_eval<GRAD>(c, x, lane, GRAD ? &gp : nullptr);
+        if (GRAD) *g = -gp;
+        return f;
+    }
+};
+
+// The optimiser (bfgs_impl.h) on -pl.
+__global__ __launch_bounds__(64) void ldsr_bfgs_update_kernel(BfgsUpdateParams prm) {
+    const int lane = threadIdx.x;
+    const int P = 6 + prm.S.p + prm.S.q;
+    const bool mine = lane < P;
+    const double lo = mine ? prm.lb[lane] : 0.0, hi = mine ? prm.ub[lane] : 0.0;
+    for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
+        const NegPlObjective obj{plg_cell(prm.S, cell, prm.lambda)};
+        bfgs_cell(obj, prm, cell, P, lane, mine, lo, hi);
+    }
+}
+
+hipError_t launch_pl_grad(const PlGradParams &prm, hipStream_t stream) {
+    if (prm.S.n_cells <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ldsr_pl_grad_kernel, dim3((unsigned)plg_waves(prm.S.n_cells)), dim3(64), 0, stream, prm);
+    return hipGetLastError();
+}
+
+hipError_t launch_bfgs_update(const BfgsUpdateParams &prm, hipStream_t stream) {
+    if (prm.S.n_cells <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ldsr_bfgs_update_kernel, dim3((unsigned)plg_waves(prm.S.n_cells)), dim3(64), 0, stream, prm);
+    return hipGetLastError();
+}

@@ -9,7 +9,14 @@ central differences in numpy for the gradient (2 (6+p+q) + 1 passes per gradient
 without gr), driven by the same optimiser (tests/bfgs_model.py), the restarts of a problem in lockstep
 so that every propagate call carries as many thetas as are still running.
 
-    python tools/bfgs_rate.py [--restarts 100] [--folds 30] [--reps 3] [--host-restarts 8] > profiles/r07_bfgs_rates.txt"""
+    python tools/bfgs_rate.py [--restarts 100] [--folds 30] [--reps 3] [--host-restarts 8] > profiles/r07_bfgs_rates.txt
+
+--objective pl: LDS_BFGS_with_update instead (ldsr_bfgs_update_batch, f = -penalized_likelihood at --lambda), on
+the T = 113 and T = 813 NP problems with a box that keeps Q, R, V1 >= 0.5: evaluations per second, the wall time
+of LDS_BFGS_with_update, and for scale the time of ldsr_penalized_lik_batch -- the value-only FIT kernel that
+computes the same number -- on the same thetas.
+
+    python tools/bfgs_rate.py --objective pl > profiles/r08_bfgs_update_rates.txt"""
 import argparse
 import json
 import os
@@ -86,13 +93,49 @@ def host_loop(eng, y, u, v, par0, lb, ub):
     return time.perf_counter() - t, passes[0], np.nanmin(vals)
 
 
+def main_pl(a):
+    import ldsr_amd as eng
+    from ldsr_amd.bfgs import start_points
+    y813, pcs, _, _ = np_problem()
+    p = q = 3
+    lb = np.concatenate([[0.0], np.full(p, -1.0), [0.0], np.full(q, -1.0), [0.5, 0.5, -1.0, 0.5]])
+    ub = np.concatenate([[1.0], np.full(p, 1.0), [1.0], np.full(q, 1.0), [1.5, 1.5, 1.0, 1.5]])
+    n = a.restarts
+    par0 = start_points(lb, ub, n, seed=1)
+    print("# tools/bfgs_rate.py --objective pl: NP data, p = q = 3, %d restarts, lambda = %g, maxit = 100, lmm = 5, factr = 1e7" % (n, a.lam))
+    print("# %s" % eng._lib.lib().ldsr_version().decode())
+    print("case                              seconds   evaluations   eval/s      iterations(mean/max)  best -pl")
+    for T in (113, 813):
+        y, u = y813[813 - T:], np.ascontiguousarray(pcs[:, 813 - T:])
+        sec, r = timed(lambda: eng.bfgs_update_batch(y, u, u, par0, lb, ub, lam=a.lam, select="min"), a.reps)
+        ev = int(r["all"]["n_eval"].sum())
+        print("%-32s %9.5f %12d %11.4g   %8.1f / %-5d %14.8g" % ("T = %d, ldsr_bfgs_update_batch" % T, sec, ev, ev / sec,
+              np.mean(r["all"]["n_iter"]), np.max(r["all"]["n_iter"]), r["value"][0]))
+        st = np.bincount(r["all"]["status"], minlength=4)
+        print("#   status: %d converged, %d maxit, %d line search, %d non-finite" % tuple(st[:4]))
+        sec, _ = timed(lambda: eng.LDS_BFGS_with_update(y, u, u, lambda_=a.lam, ub=ub, lb=lb, num_restarts=n, seed=1,
+                                                        select="min"), a.reps)
+        print("%-32s %9.5f" % ("T = %d, LDS_BFGS_with_update" % T, sec))
+        th = r["all"]["par"]
+        sec, _ = timed(lambda: eng.pl_grad(y, u, u, th, a.lam), a.reps)
+        print("%-32s %9.5f %12d %11.4g" % ("T = %d, pl_grad, values" % T, sec, n, n / sec))
+        sec, _ = timed(lambda: eng.pl_grad(y, u, u, th, a.lam, grad=True), a.reps)
+        print("%-32s %9.5f %12d %11.4g" % ("T = %d, pl_grad, with gradient" % T, sec, n, n / sec))
+        sec, _ = timed(lambda: eng.penalized_likelihood(y, u, u, th, a.lam), a.reps)
+        print("%-32s %9.5f %12d %11.4g" % ("T = %d, ldsr_penalized_lik_batch" % T, sec, n, n / sec))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--objective", choices=("ssq", "pl"), default="ssq")
+    ap.add_argument("--lambda", dest="lam", type=float, default=1.0)
     ap.add_argument("--restarts", type=int, default=100)
     ap.add_argument("--folds", type=int, default=30)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-restarts", type=int, default=8)
     a = ap.parse_args()
+    if a.objective == "pl":
+        return main_pl(a)
     import ldsr_amd as eng
     from ldsr_amd.bfgs import start_points
     y, pcs, lb, ub = np_problem()
