@@ -27,6 +27,7 @@
 // Cells are dealt statically (tol == 0) or pulled by each half from the per-series work queue
 // (tol > 0: a half whose cell has converged takes the next one while the other half goes on).
 #pragma once
+#include <type_traits>
 #include "em_scan_impl.h"
 
 // lanes per cell LPC = 32 (two cells per wave, T <= 1024) or 16 (FOUR cells per wave, one per DPP
@@ -61,6 +62,9 @@ __host__ __device__ constexpr long pair_tri_doubles(int PP, int QQ, int LPC = 32
 #endif
 #ifndef LDSR_STEADY_MIN_L      // shortest chunk whose L-1 transient steps usually reach the fixed point
 #define LDSR_STEADY_MIN_L 24
+#endif
+#ifndef LDSR_LIK_ON_DEMAND     // 0: the static-schedule steady members evaluate the likelihood in every iteration (A/B builds)
+#define LDSR_LIK_ON_DEMAND 1   // 2: ... in none (listings only: tools/loop_mix.py then counts the skipping path alone, 0 the evaluating one)
 #endif
 // read-ahead rings of the generic sweeps (pair_generic_sweeps: SPF): chunks of up to 23 steps, narrow inputs
 #ifndef LDSR_PAIR_SPF
@@ -201,10 +205,17 @@ struct PairSweepOut {
 // scan / F2, reverse scan, B2 -- em_scan_impl.h's algorithm on LPC-lane cells, see the head of this
 // file.  (x_in, v_in) is the state at the first step of the sweeps (mu1, V1; LEAD: the state at the
 // tail's first step).  hs: this lane's column of the wave's h_t strip.
-template <int PP, int QQ, int L, int LPC, bool DENSE>
+// LIKOD (likelihood on demand: the steady form's G phase under the static schedule, pair_need_lik): F2 leaves
+// out what only the likelihood reads -- dl^2 / Sigma, the folded product of the Sigma_t with its sign -- and in
+// the iterations whose likelihood IS read (wave-uniform `need_lik`) a pass of its own ahead of F2 forms them
+// from the same entry state with the same operations, so the value does not differ by a bit from the one F2
+// used to produce.  Without it likq / lsp / sneg come back zero.  Nothing that feeds the M-step sums changes.
+template <int PP, int QQ, int L, int LPC, bool DENSE, bool LIKOD = false>
 __device__ __forceinline__ void pair_generic_sweeps(PairSweepOut<PP, QQ> &o, const Theta<PP, QQ> &th,
                                                     const double *ys, double *hs, unsigned obsmask,
-                                                    int lane, int nl, int rp, double x_t1, double v_t1) {
+                                                    int lane, int nl, int rp, double x_t1, double v_t1,
+                                                    bool need_lik = true) {
+    static_assert(!LIKOD || DENSE, "likelihood on demand: fully observed series only");
     constexpr int KV = img_values(PP, QQ);
     const int vl = lane & (LPC - 1);
     auto val = [&](int j, int i) -> double { return ys[img_off(j, i, KV, LPC, L) + vl * 2]; };
@@ -416,16 +427,48 @@ __device__ __forceinline__ void pair_generic_sweeps(PairSweepOut<PP, QQ> &o, con
     // reverse affine composite of the lane's chunk (B1 of em_scan_impl.h), accumulated in time
     // order while the steps are produced: (Pi, G, H) o step_j -- no second pass over h_t
     double Pi = 1.0, G = 0.0, H = 0.0;
+    if constexpr (LIKOD) {
+        if (need_lik) {
+            if (act) {
+                double Xl = Xp, Vl = Vp, sgl = sg, rl = r0;
+                auto f2l = [&](int j) {
+                    const double e = gv_[j], bu = Jv[j];
+                    sprod *= sgl;
+                    sneg |= __double2hiint(sgl);
+                    if ((j & 7) == 7) {
+                        sexp += __builtin_amdgcn_frexp_exp(sprod);
+                        sprod = __builtin_amdgcn_frexp_mant(sprod);
+                    }
+                    const double w = Vl * rl;
+                    const double K = C * w;                    // src/EM.cpp:86
+                    const double Vul = R * w;                  // :88
+                    const double dl = fma(-C, Xl, e);
+                    const double Xul = fma(K, dl, Xl);         // :87
+                    likq = fma(dl * rl, dl, likq);             // :122
+                    Vl = fma(A2, Vul, Q);                      // :76
+                    Xl = fma(A, Xul, bu);                      // :74
+                    sgl = fma(C2, Vl, R);
+                    rl = Vl * fast_rcp(sgl * Vl);
+                };
+#pragma unroll
+                for (int j = 0; j < L - 1; j++) f2l(j);
+                if (tail) f2l(L - 1);
+            }
+            lsp = fma((double)sexp, 0.69314718055994530942, log_pos(sprod));
+        }
+    }
     auto f2 = [&](int j) {
         const bool o = DENSE || ((obsmask >> j) & 1u);
         const double e = gv_[j], bu = Jv[j];       // left there by F1
         const double r = o ? r0 : 0.0;
-        const double sl = o ? sg : 1.0;
-        sprod *= sl;
-        sneg |= __double2hiint(sl);
-        if ((j & 7) == 7) {
-            sexp += __builtin_amdgcn_frexp_exp(sprod);
-            sprod = __builtin_amdgcn_frexp_mant(sprod);
+        if constexpr (!LIKOD) {
+            const double sl = o ? sg : 1.0;
+            sprod *= sl;
+            sneg |= __double2hiint(sl);
+            if ((j & 7) == 7) {
+                sexp += __builtin_amdgcn_frexp_exp(sprod);
+                sprod = __builtin_amdgcn_frexp_mant(sprod);
+            }
         }
         const double w = Vp * r;
         const double K = C * w;                    // src/EM.cpp:86
@@ -433,7 +476,7 @@ __device__ __forceinline__ void pair_generic_sweeps(PairSweepOut<PP, QQ> &o, con
         else Vu = fma(-(C2 * w), Vp, Vp);
         const double dl = fma(-C, Xp, e);
         Xu = fma(K, dl, Xp);                       // :87
-        likq = fma(dl * r, dl, likq);              // :122
+        if constexpr (!LIKOD) likq = fma(dl * r, dl, likq);   // :122
         const double Vp1 = fma(A2, Vu, Q);         // :76
         const double Xp1 = fma(A, Xu, bu);         // :74
         sg = fma(C2, Vp1, R);
@@ -466,7 +509,7 @@ __device__ __forceinline__ void pair_generic_sweeps(PairSweepOut<PP, QQ> &o, con
         if (tail) f2(L - 1);
     }
     tLv = fma(Xu, Xu, Vu);                                                // Xs^2 + Vs at T-1 (in lastLane)
-    lsp = fma((double)sexp, 0.69314718055994530942, log_pos(sprod));
+    if constexpr (!LIKOD) lsp = fma((double)sexp, 0.69314718055994530942, log_pos(sprod));
 
     // ------------------------------------------------ reverse scan of the chunk composites
 #define RSCAN_ROUND(n)                                                     \
@@ -1136,56 +1179,79 @@ __device__ __forceinline__ PairVarBlk pair_var_block(double V1, double A, double
     return b;
 }
 
-// ---- the rest of an iteration for the halves in `active` (the cells whose sweeps just ran): one
-// reduction per half, likelihood, stop rule, M-step; a cell that stops stores its result and -- work
-// queue -- its half pulls the next one.  The other halves keep their state untouched.
-template <int PP, int QQ, bool QUEUE>
-__device__ __forceinline__ void pair_steady_finish(const PairEnv &E, PairCarry<PP, QQ> &cs, const PairSweepOut<PP, QQ> &o,
-                                                   double addTx1x, double addPall, bool active, int lane, int c0,
-                                                   int nc, int lastLane) {
+// ---- the reduction of an iteration's sums over each half, and its likelihood.  WL: with the likelihood; without
+// it likq / lsp take no slot of the reduction (the summation tree of every other value is the same lane pairing
+// whatever its slot: the M-step sums do not change by a bit) and cs.lik is not evaluated.  (A function template, not
+// a lambda of pair_steady_finish: as a lambda it moved the register assignment of the work-queue members.)
+template <int PP, int QQ, bool WL>
+__device__ __forceinline__ void pair_steady_reduce(const PairEnv &E, PairCarry<PP, QQ> &cs, const PairSweepOut<PP, QQ> &o,
+                                                   Sums<PP, QQ> &S, double addTx1x, double addPall, bool active,
+                                                   int lane, int lastLane) {
     constexpr int LPC = 32;
-    PAIR_TICK_REFS
-    const int vl = lane & 31, hbase = lane & 32;
-    const int P = 6 + E.p + E.q;
-    Sums<PP, QQ> S;
+    const int hbase = lane & 32;
+    constexpr int NB = WL ? 5 : 3;
+    constexpr int NR = NB + QQ + 2 * PP;
+    double red[NR];
+    red[0] = o.aSyx; red[1] = o.aTx1x; red[2] = o.aPall;
+    if constexpr (WL) { red[3] = o.likq; red[4] = o.lsp; }
+#pragma unroll
+    for (int q_ = 0; q_ < QQ; q_++) red[NB + q_] = o.aSxv[q_];
+#pragma unroll
+    for (int p_ = 0; p_ < PP; p_++) { red[NB + QQ + p_] = o.aTx1u[p_]; red[NB + QQ + PP + p_] = o.aTux[p_]; }
+    // recursive halving over the half's 32 lanes (em_scan_impl.h), then every lane fetches
+    // the totals from their home lanes of its own half
+    red_rounds<NR, LPC / 2>(red, lane);
     {
-        constexpr int NB = 5;
-        constexpr int NR = NB + QQ + 2 * PP;
-        double red[NR];
-        red[0] = o.aSyx; red[1] = o.aTx1x; red[2] = o.aPall; red[3] = o.likq; red[4] = o.lsp;
+        const double tt = red[0];
 #pragma unroll
-        for (int q_ = 0; q_ < QQ; q_++) red[NB + q_] = o.aSxv[q_];
+        for (int i = 0; i < NR; i++) red[i] = shfl_d(tt, hbase | red_home(i, NR, LPC));
+    }
+    S.X0 = shfl_d(o.X0v, hbase);               // :218
+    S.V0 = shfl_d(o.V0v, hbase);               // :219
+    const double termLast = shfl_d(o.tLv, hbase | lastLane);
+    red[1] += addTx1x; red[2] += addPall;      // (steady form: the closed-form variance sums; else 0)
+    const double term0 = fma(S.X0, S.X0, S.V0);
+    const unsigned long long negm = WL ? __ballot(o.sneg < 0) : 0ull;
+    const bool neg = ((negm >> hbase) & ((1ull << LPC) - 1ull)) != 0;   // log of a negative Sigma
+    S.Syx = red[0]; S.Tx1x = red[1];
+    S.Sxx = red[2];
 #pragma unroll
-        for (int p_ = 0; p_ < PP; p_++) { red[NB + QQ + p_] = o.aTx1u[p_]; red[NB + QQ + PP + p_] = o.aTux[p_]; }
-        // recursive halving over the half's 32 lanes (em_scan_impl.h), then every lane fetches
-        // the totals from their home lanes of its own half
-        red_rounds<NR, LPC / 2>(red, lane);
-        {
-            const double tt = red[0];
+    for (int q_ = 0; q_ < QQ; q_++) S.Sxv[q_] = red[NB + q_];
 #pragma unroll
-            for (int i = 0; i < NR; i++) red[i] = shfl_d(tt, hbase | red_home(i, NR, LPC));
-        }
-        S.X0 = shfl_d(o.X0v, hbase);               // :218
-        S.V0 = shfl_d(o.V0v, hbase);               // :219
-        const double termLast = shfl_d(o.tLv, hbase | lastLane);
-        red[1] += addTx1x; red[2] += addPall;      // (steady form: the closed-form variance sums; else 0)
-        const double term0 = fma(S.X0, S.X0, S.V0);
-        const unsigned long long negm = __ballot(o.sneg < 0);
-        const bool neg = ((negm >> hbase) & ((1ull << LPC) - 1ull)) != 0;   // log of a negative Sigma
-        S.Syx = red[0]; S.Tx1x = red[1];
-        S.Sxx = red[2];
-#pragma unroll
-        for (int q_ = 0; q_ < QQ; q_++) S.Sxv[q_] = red[NB + q_];
-#pragma unroll
-        for (int p_ = 0; p_ < PP; p_++) { S.Tx1u[p_] = red[NB + QQ + p_]; S.Tux[p_] = red[NB + QQ + PP + p_]; }
-        S.Txx = red[2] - termLast;
-        S.Tx1x1 = red[2] - term0;
+    for (int p_ = 0; p_ < PP; p_++) { S.Tx1u[p_] = red[NB + QQ + p_]; S.Tux[p_] = red[NB + QQ + PP + p_]; }
+    S.Txx = red[2] - termLast;
+    S.Tx1x1 = red[2] - term0;
+    if constexpr (WL) {
         if (active) {
             cs.lik2 = cs.lik1;
             cs.lik1 = cs.lik;
             cs.lik = (-0.5 * E.n_obs * LDSR_LOG_2PI - 0.5 * (red[3] + red[4])) / E.n_obs;   // :113-124
             if (neg) cs.lik = NAN;
         }
+    } else {
+        // not evaluated: nothing reads it (tol <= 0, no trace, no cell of the wave at its last iteration, no
+        // interrupt poll); a cell that WAITS through a later poll and is stopped there reports NaN, not a stale value
+        if (active) cs.lik = NAN;
+    }
+}
+
+// ---- the rest of an iteration for the halves in `active` (the cells whose sweeps just ran): one
+// reduction per half, likelihood, stop rule, M-step; a cell that stops stores its result and -- work
+// queue -- its half pulls the next one.  The other halves keep their state untouched.
+template <int PP, int QQ, bool QUEUE>
+__device__ __forceinline__ void pair_steady_finish(const PairEnv &E, PairCarry<PP, QQ> &cs, const PairSweepOut<PP, QQ> &o,
+                                                   double addTx1x, double addPall, bool active, int lane, int c0,
+                                                   int nc, int lastLane, bool need_lik) {
+    constexpr int LPC = 32;
+    PAIR_TICK_REFS
+    const int vl = lane & 31, hbase = lane & 32;
+    const int P = 6 + E.p + E.q;
+    Sums<PP, QQ> S;
+    if constexpr (QUEUE) {
+        pair_steady_reduce<PP, QQ, true>(E, cs, o, S, addTx1x, addPall, active, lane, lastLane);
+    } else {
+        if (need_lik) pair_steady_reduce<PP, QQ, true>(E, cs, o, S, addTx1x, addPall, active, lane, lastLane);
+        else pair_steady_reduce<PP, QQ, false>(E, cs, o, S, addTx1x, addPall, active, lane, lastLane);
     }
     SCAN_TICK(8)       // reduction, likelihood
     int abort_now = 0;
@@ -1243,6 +1309,20 @@ __device__ __forceinline__ void pair_steady_finish(const PairEnv &E, PairCarry<P
     }
 }
 
+// ---- Likelihood on demand (static schedule only: the work-queue members evaluate it every iteration).  The
+// likelihood of an iteration is read by the stop rule (tol > 0; a comparison with tol <= 0 or NaN is never
+// true, src/EM.cpp:272), by the trace, by the result of a cell that stops -- at niter, or at an interrupt
+// poll -- and by nothing else: a run of a fixed number of iterations throws away all but the last.  Wave
+// uniform; `active` = the halves whose iteration is about to run (a half that evaluates a likelihood it did
+// not need does no harm).
+template <int PP, int QQ, bool QUEUE>
+__device__ __forceinline__ bool pair_need_lik(const PairEnv &E, const PairCarry<PP, QQ> &cs, bool active) {
+    if constexpr (QUEUE || LDSR_LIK_ON_DEMAND == 0) return true;
+    else if constexpr (LDSR_LIK_ON_DEMAND == 2) return false;
+    else return __any(E.tol > 0.0 || E.liks != nullptr || (active && cs.it + 1 >= E.niter) ||
+                      (E.abort != nullptr && ((cs.wit + 1) & 63) == 0)) != 0;
+}
+
 // ---- G phase: generic iterations for the halves whose cell fails the verdict (`slow`, from the S loop's
 // verdict on entry: at least one iteration runs), until no cell of the wave fails.  A real function: the
 // generic sweeps keep 244 VGPRs busy, and entered once per slow episode the ~250 scratch accesses of
@@ -1278,10 +1358,11 @@ __device__ __attribute__((noinline)) PairCarry<PP, QQ> pair_steady_g_phase(PairE
     double *hs = smem + pair_image_doubles(L, PP, QQ, LPC) + (long)wave * pair_strip_doubles(L) + lane;
     do {
         SCAN_TICK(7)
+        const bool need_lik = pair_need_lik<PP, QQ, QUEUE>(E, cs, slow);
         PairSweepOut<PP, QQ> o;
-        pair_generic_sweeps<PP, QQ, L, LPC, true>(o, cs.th, ys, hs, 0u, lane, nl, rp, cs.th.mu1, cs.th.V1);
+        pair_generic_sweeps<PP, QQ, L, LPC, true, !QUEUE>(o, cs.th, ys, hs, 0u, lane, nl, rp, cs.th.mu1, cs.th.V1, need_lik);
         SCAN_TICK(6)       // the generic sweeps
-        pair_steady_finish<PP, QQ, QUEUE>(E, cs, o, 0.0, 0.0, slow, lane, c0, nc, nl - 1);
+        pair_steady_finish<PP, QQ, QUEUE>(E, cs, o, 0.0, 0.0, slow, lane, c0, nc, nl - 1, need_lik);
         const PairVarBlk vb = pair_var_block<L>(cs.th.V1, cs.th.A, cs.th.C, cs.th.Q, cs.th.R, cs.alive, vl, hbase, shape_ok);
         slow = cs.alive && !vb.st;
     } while (__any(slow));
@@ -1355,6 +1436,7 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
             const bool st = vb.st;
             slow = cs.alive && !st;
             if (__builtin_expect(__any(slow), 0)) break;
+            const bool need_lik = pair_need_lik<PP, QQ, QUEUE>(E, cs, cs.alive);
             // what the sweeps leave in every lane
             double likq = 0.0, lsp = 0.0, tLv = 0.0, X0v = 0.0, V0v = 0.0;
             double addPall = 0.0, addTx1x = 0.0;    // closed-form variance sums of the steady region
@@ -1399,12 +1481,15 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
             const double trJ = J;
             const double trG = fma(-J, Xp1, Xu);
             const double trH = fma(-J, AVu, Vu);
-            const double trLq = trl ? dl * r0 * dl : 0.0;           // :122
-            const double lg = log_pos(vb.sg);
-            const double trLg = trl ? lg : 0.0;
+            double trLq = 0.0, lg = 0.0, trLg = 0.0;                // the likelihood's share of the block
+            if (need_lik) {
+                trLq = trl ? dl * r0 * dl : 0.0;                    // :122
+                lg = log_pos(vb.sg);
+                trLg = trl ? lg : 0.0;
+            }
             const int src = hbase | (LPC - 1);
             const double cK = shfl_d(K, src), cJ = shfl_d(J, src), cr = shfl_d(r0, src), cVu = shfl_d(Vu, src);
-            const double ch = shfl_d(trH, src), clg = shfl_d(lg, src), X_tr = shfl_d(Xp, src);
+            const double ch = shfl_d(trH, src), clg = need_lik ? shfl_d(lg, src) : 0.0, X_tr = shfl_d(Xp, src);
 
             SCAN_TICK(0)       // iteration constants, transient block, verdict
             if (st) {          // (idle halves -- no cell left -- skip the sweeps)
@@ -1481,10 +1566,28 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
                 if (vl == 0) Xq = X_tr;
                 // ---- F2: the reference's mean expressions with the steady gains
                 double lq = 0.0, Xuq = 0.0;
+                // (static schedule: dl^2 is summed only in the iterations whose likelihood is read, by a pass of
+                // its own ahead of F2 -- the same operations from the same entry state, the same bits)
+                constexpr bool LOD = !QUEUE;
+                if constexpr (LOD) {
+                    if (need_lik) {
+                        double Xl = Xq;
+                        auto f2l = [&](int j, double bu) {
+                            const double dlq = fma(-C, Xl, gv_[j]);
+                            lq = fma(dlq, dlq, lq);                    // :122 (times 1/Sigma below)
+                            Xl = fma(A, fma(cK, dlq, Xl), bu);         // :87, :74
+                        };
+                        if (body) {
+#pragma unroll
+                            for (int j = 0; j < L - 1; j++) f2l(j, hs[j * 64]);
+                        }
+                        if (tail_s) f2l(L - 1, buLast);
+                    }
+                }
                 auto f2s = [&](int j, double bu) {
                     const double e = gv_[j];
                     const double dlq = fma(-C, Xq, e);
-                    lq = fma(dlq, dlq, lq);                            // :122 (times 1/Sigma below)
+                    if constexpr (!LOD) lq = fma(dlq, dlq, lq);        // :122 (times 1/Sigma below)
                     Xuq = fma(cK, dlq, Xq);                            // :87
                     const double Xq1 = fma(A, Xuq, bu);                // :74
                     double g = fma(-cJ, Xq1, Xuq);
@@ -1520,8 +1623,10 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
                 __builtin_amdgcn_sched_barrier(LDSR_STEADY_SBMASK);
                 tLv = fma(Xuq, Xuq, cVu);
                 const int nst = (body ? L - 1 : 0) + (tail_s ? 1 : 0);    // steady steps of this lane
-                likq = fma(cr, lq, trLq);
-                lsp = fma((double)nst, clg, trLg);
+                if (need_lik) {
+                    likq = fma(cr, lq, trLq);
+                    lsp = fma((double)nst, clg, trLg);
+                }
                 // ---- reverse composite of the chunk (constant multiplier J), reverse scan
                 double Pi = 1.0, G = 0.0;
                 if (tail_s) { G = gv_[L - 1]; Pi = cJ; }
@@ -1636,7 +1741,7 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
             for (int q_ = 0; q_ < QQ; q_++) o.aSxv[q_] = aSxv[q_];
 #pragma unroll
             for (int p_ = 0; p_ < PP; p_++) { o.aTx1u[p_] = aTx1u[p_]; o.aTux[p_] = aTux[p_]; }
-            pair_steady_finish<PP, QQ, QUEUE>(E, cs, o, addTx1x, addPall, st, lane, c0, nc, lastLane);
+            pair_steady_finish<PP, QQ, QUEUE>(E, cs, o, addTx1x, addPall, st, lane, c0, nc, lastLane, need_lik);
         }
         if (__builtin_expect(!__any(slow), 1)) break;      // every cell of the wave is done
         // ================================================================= G phase: generic iterations
