@@ -1,9 +1,10 @@
 """Host model of the smoother family -- Kalman_smoother (src/EM.cpp:22-131), the penalty of
-penalized_likelihood (R/LDS_GA.R:34-40), propagate (src/EM.cpp:295-356) and Mstep (src/EM.cpp:139-229) --
-in plain numpy, serial in time and vectorised over the rows of a packed theta [n, 6+p+q] =
+penalized_likelihood (R/LDS_GA.R:34-40), propagate (src/EM.cpp:295-356), Mstep (src/EM.cpp:139-229) and the EM
+loop LDS_EM made of them (src/EM.cpp:245-280) -- in plain numpy, serial in time and vectorised over the rows of a packed theta [n, 6+p+q] =
 [A, B(p), C, D(q), Q, R, mu1, V1].  It works in float64 and in numpy.longdouble: the longdouble run is the
 extended-precision yardstick that says whether a gap between a device kernel and the fp64 oracle belongs to the
-kernel or to the oracle (tests/test_smoother_model_host.py, tests/test_gpu_smoother_family.py).
+kernel or to the oracle (tests/test_smoother_model_host.py, tests/test_gpu_smoother_family.py; the EM loop:
+tests/test_em_model_host.py, tests/test_gpu_em_family.py).
 
 A second statement of the recursions, independent of tests/plgrad_model.py and of oracle/ldsr_oracle.c: the
 reference's expressions in the reference's order, its absent-input branches (u or v None), J[T-1] of
@@ -150,7 +151,7 @@ def mstep(y, u, v, fit, dtype=np.float64):
     p, q = _dims(u, v)
     yd, obs, u, v = _inputs(y, u, v, dtype)
     T = yd.size
-    X, V, J = (np.atleast_2d(np.asarray(fit[k], dtype=np.float64)).astype(dtype) for k in "XVJ")
+    X, V, J = (np.atleast_2d(np.asarray(fit[k])).astype(dtype) for k in "XVJ")     # (a longdouble fit stays one)
     n = X.shape[0]
     th = np.zeros((n, 6 + p + q), dtype=dtype)              # B, D start at 0 (:154, :186)
     yo, n_obs = yd[obs], dtype(np.count_nonzero(obs))
@@ -198,3 +199,41 @@ def mstep(y, u, v, fit, dtype=np.float64):
             th[i, 2 + p + q], th[i, 3 + p + q] = Qn, Rn
             th[i, 4 + p + q], th[i, 5 + p + q] = x[0], Vi[0]   # :218-219
     return th
+
+
+def em(theta0, y, u, v, niter=1000, tol=1e-5, dtype=np.float64):
+    """LDS_EM (src/EM.cpp:245-280) for every row of theta0, from smoother() and mstep() above: E, M, E, then
+    M and E per iteration; a row stops after iteration i >= 2 once |lik_i - lik_{i-1}| and |lik_{i-1} - lik_{i-2}|
+    are both below tol (:272), or after niter iterations.  -> {"theta" [n, 6+p+q], "lik" [n], "liks" [n, niter]
+    (NaN behind n_iter) in `dtype`, "n_iter" [n] (the reference's lastIter), "margin" [n] float64}.  margin is
+    the smallest | |dlik| - tol | over the differences the row's stop decisions read: a result whose liks are
+    nearer than margin / 2 to this one's stops at the same iteration."""
+    dtype = np.dtype(dtype).type
+    if niter < 2:
+        raise ValueError("niter must be >= 2 (the reference reads lik[1], src/EM.cpp:256)")
+    theta = np.atleast_2d(np.asarray(theta0)).astype(dtype)
+    n = theta.shape[0]
+    liks = np.full((n, niter), np.nan, dtype=dtype)
+    n_iter = np.full(n, 2, dtype=np.int32)
+    margin = np.full(n, np.inf)
+    fit = smoother(theta, y, u, v, dtype=dtype)                 # i = 0 (:251-253)
+    liks[:, 0] = fit["lik"]
+    theta = mstep(y, u, v, fit, dtype=dtype)
+    fit = smoother(theta, y, u, v, dtype=dtype)                 # i = 1 (:255-256)
+    liks[:, 1] = fit["lik"]
+    lik = np.array(fit["lik"], dtype=dtype)
+    run = np.arange(n)                                          # the rows still iterating
+    for i in range(2, niter):                                   # :259-275
+        th = mstep(y, u, v, fit, dtype=dtype)
+        fit = smoother(th, y, u, v, dtype=dtype)
+        theta[run], lik[run], liks[run, i], n_iter[run] = th, fit["lik"], fit["lik"], i + 1
+        with np.errstate(invalid="ignore"):
+            d1, d2 = np.abs(liks[run, i] - liks[run, i - 1]), np.abs(liks[run, i - 1] - liks[run, i - 2])
+            m = np.minimum(np.abs(d1 - dtype(tol)), np.abs(d2 - dtype(tol))).astype(np.float64)
+            margin[run] = np.fmin(margin[run], m)
+            go = ~((d1 < tol) & (d2 < tol))
+        if not go.any():
+            break
+        run = run[go]
+        fit = {k: fit[k][go] for k in "XVJ"}
+    return {"theta": theta, "lik": lik, "liks": liks, "n_iter": n_iter, "margin": margin}

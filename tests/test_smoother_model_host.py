@@ -134,20 +134,34 @@ def test_model_reproduces_the_reference_known_answers(p1case, npcase, refdata, d
 
 
 def test_model_em_loop_reproduces_the_reference_convergence(p1case):
-    """LDS_EM (src/EM.cpp:245-280) from the model's smoother and M-step alone: 68 iterations to
-    lik = -0.039093, the reference's own known answer (tests/testthat/test-LDS-EM.R:36-41)."""
+    for dtype in (np.float64, np.longdouble):
+        _em_loop_reproduces_the_reference_convergence(p1case, dtype)
+
+
+def _em_loop_reproduces_the_reference_convergence(p1case, dtype):
+    """LDS_EM (src/EM.cpp:245-280) as the model's em(): 68 iterations to lik = -0.039093, the reference's own
+    known answer (tests/testthat/test-LDS-EM.R:36-41), in float64 and in longdouble; the trace, the margin of
+    the stop decisions and the rows' independence."""
     c = p1case
     y, u, v, tol = c["y"], c["u"], c["v"], 1e-5
-    theta, liks = c["theta0"], []
-    for i in range(100):
-        if i > 0:
-            theta = SM.mstep(y, u, v, fit)[0]
-        fit = SM.smoother(theta, y, u, v)
-        liks.append(float(fit["lik"][0]))
-        if i >= 2 and abs(liks[i] - liks[i - 1]) < tol and abs(liks[i - 1] - liks[i - 2]) < tol:
-            break
-    assert len(liks) == 68 and liks[-1] == pytest.approx(-0.039093, abs=1e-6)
-    assert theta[0] == pytest.approx(0.59893129323481986, rel=1e-9)
+    r = SM.em(c["theta0"], y, u, v, niter=100, tol=tol, dtype=dtype)
+    assert r["theta"].dtype == dtype and r["liks"].dtype == dtype and r["liks"].shape == (1, 100)
+    assert r["n_iter"][0] == 68 and float(r["lik"][0]) == pytest.approx(-0.039093, abs=1e-6)
+    assert float(r["theta"][0, 0]) == pytest.approx(0.59893129323481986, rel=1e-9)
+    liks = r["liks"][0]
+    assert np.all(np.isfinite(liks[:68])) and np.all(np.isnan(liks[68:])) and liks[67] == r["lik"][0]
+    d = np.abs(np.diff(np.asarray(liks[:68], dtype=np.float64)))
+    assert d[66] < tol and d[65] < tol and not (d[65] < tol and d[64] < tol)      # stopped exactly there
+    assert 0 < r["margin"][0] <= min(abs(d[66] - tol), abs(d[65] - tol), abs(d[64] - tol)) * (1 + 1e-6)
+    # a row stops on its own: a second row goes on to the cap and the first keeps what it had when it stopped
+    # (to rounding: numpy sums B u in another order for two rows)
+    th2 = np.stack([c["theta0"], c["theta0"]])
+    th2[1, 0], th2[1, 8] = 0.9, 0.1
+    r2 = SM.em(th2, y, u, v, niter=80, tol=tol, dtype=dtype)
+    assert r2["n_iter"][0] == 68 and r2["n_iter"][1] != 68 and np.all(np.isnan(r2["liks"][0, 68:]))
+    assert parity_close(np.asarray(r2["liks"][0, :68], dtype=np.float64), np.asarray(liks[:68], dtype=np.float64), 1e-10, 0)
+    assert parity_close(np.asarray(r2["theta"][0], dtype=np.float64), np.asarray(r["theta"][0], dtype=np.float64), 1e-9, 1e-12)
+    assert np.all(SM.em(c["theta0"], y, u, v, niter=2, tol=tol, dtype=dtype)["n_iter"] == 2)
 
 
 def test_model_missing_values_and_solver():
