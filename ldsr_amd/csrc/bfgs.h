@@ -1,6 +1,6 @@
 // bfgs.h -- launch interface of the L-BFGS learner (bfgs.hip): LDS_BFGS, R/LDS_GA.R:155-184, by the
 // specification in INTEGRATION.md ("The bound-constrained L-BFGS").  Included by bfgs.hip and
-// ldsr_api.hip only.
+// api_bfgs.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 

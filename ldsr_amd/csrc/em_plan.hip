@@ -1,6 +1,6 @@
 // em_plan.hip -- which EM kernel a launch runs: AUTO's rules, the support checks of the explicit
 // algorithms, the schedule and the kernel's name, in one place.  Host code only, no HIP calls: every
-// EM launch (ldsr_api.hip em_batch_device_impl) and the plan queries of the C ABI (ldsr_em_plan,
+// EM launch (api_em.hip em_batch_device_impl) and the plan queries of the C ABI (ldsr_em_plan,
 // ldsr_em_plan_lead, ldsr_em_workspace_bytes) ask em_plan(); the queries assume a launch that fills
 // the device.
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // ga.h -- launch interface of the island genetic algorithm (ga.hip): LDS_GA, R/LDS_GA.R:54-82, by the
-// specification in INTEGRATION.md ("The island GA").  Included by ga.hip and ldsr_api.hip only.
+// specification in INTEGRATION.md ("The island GA").  Included by ga.hip and api_ga.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -2,7 +2,7 @@
 // R/LDS_GA.R:54-82; the algorithm is this project's own specification, INTEGRATION.md "The island GA").
 //
 // A generation is two launches: the smoother's scalar-only fitness pass over the current population
-// buffer (ldsr_api.hip), then ldsr_ga_breed_kernel, one workgroup per island:
+// buffer (api_ga.hip), then ldsr_ga_breed_kernel, one workgroup per island:
 //   * problem-wide bookkeeping.  Every island's workgroup reduces all K n fitness values of its problem
 //     and reaches the same verdict (improved / stall / done) from the state of parity g & 1; island 0
 //     alone writes the state of parity (g + 1) & 1, the trace and the best gene vector.  Nothing a

@@ -1,4 +1,4 @@
-// ldsr_kernels.h -- host-visible launch interface between the C ABI (ldsr_api.hip) and the kernels.
+// ldsr_kernels.h -- host-visible launch interface between the C ABI (api_*.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 

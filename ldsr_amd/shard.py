@@ -13,14 +13,14 @@ against 1.18 / 1.22 / 1.32 for contiguous ranges of the flattened grid, round 2'
 holds every series (<= 100 KB each).  The only cross-rank step is the gather of 8*(P+3) bytes per
 cell before the per-series argmax (R/LDS_reconstruction.R:50-58); it uses whatever
 torch.distributed backend the caller initialised (RCCL on GPUs, gloo in the CPU tests).  The
-library cuts the same way for callers without torch.distributed (make_slices, ldsr_api.hip)."""
+library cuts the same way for callers without torch.distributed (make_slices, api_grid.hip)."""
 import numpy as np
 
 
 def rank_slice(n_cells, world, rank, series=0):
     """Contiguous range [lo, hi): the rank's part of ONE series' n_cells restarts -- part
     (rank + series) mod world of the `world` contiguous parts (the same rule as make_slices in
-    ldsr_api.hip)."""
+    api_grid.hip)."""
     k = (rank + series) % world
     lo = n_cells * k // world
     hi = n_cells * (k + 1) // world

@@ -152,6 +152,67 @@ def test_argument_validation_without_gpu():
             assert call(lb, ub) == 1 and L.ldsr_last_error() == msg, (noun, L.ldsr_last_error())
 
 
+def test_every_host_unit_reports_through_the_one_error_slot():
+    """The entries live in one translation unit per family (ldsr_amd/csrc/api_*.hip) and the error slot in
+    another (host_runtime.hip): an invalid call of one entry of every unit returns its code, and
+    ldsr_last_error() then holds that entry's own message."""
+    from ldsr_amd import _lib
+    L = _lib.lib()
+    P = 8
+    y = (C.c_double * 4)(0.1, -0.2, 0.3, 0.0)
+    off = (C.c_int * 2)(0, 1)
+    th, out = (C.c_double * P)(*([0.5] * P)), (C.c_double * P)()
+    lb, ub = (C.c_double * P)(*([0.1] * P)), (C.c_double * P)(*([0.9] * P))
+    val, it, st = (C.c_double * 1)(), (C.c_int * 1)(), (C.c_int * 1)()
+    calls = (
+        # api_em.hip: d_workspace = NULL
+        (lambda: L.ldsr_em_batch_device(0, None, 1, 4, 1, 1, y, None, None, 0, off, th, 10, 1e-5, 0, out, val, it, st,
+                                        None, None, 0), b"NULL output / workspace pointer"),
+        # api_grid.hip: T = 1
+        (lambda: L.ldsr_em_batch(0, 1, 1, 1, 1, y, None, None, 0, off, th, 10, 1e-5, 0, out, val, it, st, None),
+         b"T must be"),
+        # api_fit.hip: theta = NULL
+        (lambda: L.ldsr_smooth_batch(0, 1, 4, 1, 1, y, None, None, 0, off, None, 1, None, None, None, None, val),
+         b"theta and lik must not be NULL"),
+        # api_ga.hip: num_islands = 0
+        (lambda: L.ldsr_ga_batch(0, 1, 4, 1, 1, y, None, None, 0, lb, ub, 1.0, 0, 8, 5, 3, 1, None, 0, out, val, it,
+                                 None, None, None), b"num_islands must be >= 1"),
+        # api_bfgs.hip: maxit = 0, lambda = NaN
+        (lambda: L.ldsr_bfgs_batch(0, 1, 4, 1, 1, y, None, None, 0, off, th, lb, ub, 0, 5, 1e7, 0.0, 1, 0, None, None,
+                                   None, None, None, st, out, val, None, None, None, None, None),
+         b"maxit must be >= 1"),
+        (lambda: L.ldsr_pl_grad_batch(0, 1, 4, 1, 1, y, None, None, 0, off, th, float("nan"), val, None),
+         b"lambda must be finite"),
+        # api_simulate.hip: T = 0 (tests/test_simulate_host.py test_argument_validation)
+        (lambda: L.ldsr_simulate_batch(0, 1, 0, 1, 1, None, None, 0, th, None, 2, 0, 1, 5, None, out, None, None),
+         b"T must be"),
+    )
+    for call, msg in calls:
+        assert call() == 1 and msg in L.ldsr_last_error(), (msg, L.ldsr_last_error())
+    # every message above was this thread's last one, and the next call's replaces it
+    assert calls[0][0]() == 1 and L.ldsr_last_error() == b"NULL output / workspace pointer"
+
+
+def test_worker_thread_message_reaches_the_caller():
+    """Without a GPU both slices of a two-device call fail at their first HIP call, one of them on a library
+    worker thread: run_slices (api_grid.hip) reads each thread's message through host_runtime.hip's accessor
+    and fails on the caller's thread with the device's prefix."""
+    from ldsr_amd import _lib
+    L = _lib.lib()
+    if L.ldsr_device_count() > 0:
+        pytest.skip("GPU present")
+    P = 8
+    y = (C.c_double * 4)(0.1, -0.2, 0.3, 0.0)
+    off = (C.c_int * 2)(0, 2)       # one series, two restarts: one cell for each device
+    th0, th = (C.c_double * (2 * P))(*([0.5] * (2 * P))), (C.c_double * (2 * P))()
+    lik, it, st = (C.c_double * 2)(), (C.c_int * 2)(), (C.c_int * 2)()
+    devices = (C.c_int * 2)(0, 1)
+    rc = L.ldsr_em_batch_multi(2, devices, 1, 4, 1, 1, y, None, None, 0, off, th0, 5, 1e-5, 0, th, lik, it, st, None)
+    msg = L.ldsr_last_error()
+    assert rc == 3, (rc, msg)      # LDSR_EHIP
+    assert msg.startswith(b"device 0: ") and len(msg) > len(b"device 0: "), msg
+
+
 def test_cell_offsets_validation_without_gpu():
     """The [S+1] cell offsets are checked once (api._offsets) for every entry that takes them with a theta per
     cell: same ValueError texts from em_batch, em_restart_grid, ssq_train and bfgs_batch, before the library is
