@@ -43,6 +43,8 @@
  *                            replicates of each of n_models thetas in one launch; with the uniforms
  *                            R would draw (ldsr_simulate_draw_count) the result is set.seed(k);
  *                            LDS_rep(...) draw for draw
+ *   ldsr_pcr_batch           the benchmark model R/PCR.R: every (member, fold) least-squares fit of cvPCR /
+ *                            PCR_ensemble_selection (one_pcr_cv :101-107) and PCR_reconstruction's lm + predict
  *
  * Data conventions (identical to the bytes R hands to .Call):
  *   y      [n_series][T]        double, NaN / NA_real_ = missing
@@ -399,6 +401,29 @@ int ldsr_simulate_batch_device(int device, void *stream, int n_models, int T, in
                                int first_rep, int exp_trans, unsigned long long seed,
                                const double *d_uniforms, const long long *d_offsets,
                                double *d_simX, double *d_simY, double *d_simQ);
+
+/* Principal-component regression, the reference's benchmark model (R/PCR.R): one_pcr_cv (:101-107) for every
+ * (member, fold) cell of cvPCR / PCR_ensemble_selection (:164, :220, :228) and the lm + predict of
+ * PCR_reconstruction (:49-50, :76-77), all cells in ONE launch.  Cell (m, f) fits y ~ 1 + X_m by a Householder QR
+ * (intercept first, the member's columns in order, no pivoting -- the method class of stats::.lm.fit, not the
+ * normal equations) on the rows with heldout[f][i] == 0 and y[i] finite, then predicts the rows of Xpred_m.
+ *   k        [n_members] columns of each member, 1 .. 16 (larger: LDSR_EUNSUPPORTED); members may differ
+ *   X        member blocks, each n x k[m] column-major (the bytes of an R matrix), concatenated
+ *   y        [n]; NaN, NA and +-Inf rows never train (na.omit)
+ *   heldout  [n_folds][n] bytes, 0 / 1; n_folds = 1 with an all-zero row is the plain fit
+ *   Xpred    member blocks, each N x k[m] column-major, concatenated; NULL: predict X's own rows (N must be n)
+ *   pred     [n_members][n_folds][N] x_t' beta        lev   likewise, h_t = |R^-T x_t|^2 = x_t'(X'X)^-1 x_t
+ *   coef     [n_members][n_folds][17]: intercept, slopes, NaN beyond k[m] + 1
+ *   sigma    [n_members][n_folds] sqrt(RSS / df), NaN when df = 0      df  likewise, n_train - (k[m] + 1)
+ *   status   [n_members][n_folds] LDSR_CELL_OK, or LDSR_CELL_SINGULAR (pred, lev, coef, sigma NaN): fewer
+ *            training rows than k[m] + 1, or a column whose norm after the reflections before it is <= 1e-7 of
+ *            its original norm -- .lm.fit's tolerance used as a flag where LINPACK would pivot
+ * lev, coef, sigma, df may each be NULL.  Host pointers.  A cell's result does not depend on the other cells of
+ * the call.  Limits: n >= 2 and n * (max k + 2) <= 18432 (a cell's design lives in LDS: n <= 1024 at k = 16,
+ * n <= 6144 at k = 1; larger: LDSR_EUNSUPPORTED); N is unbounded. */
+int ldsr_pcr_batch(int device, int n_members, int n, const int *k, const double *X, const double *y, int n_folds,
+                   const unsigned char *heldout, int N, const double *Xpred, double *pred, double *lev,
+                   double *coef, double *sigma, int *df, int *status);
 
 /* User interrupts during a run (the reference calls Rcpp::checkUserInterrupt() every 100 EM
  * iterations, src/EM.cpp:261-262).  While a callback is registered, the thread that called an

@@ -74,6 +74,8 @@ SIGNATURES = {
     "ldsr_simulate_batch_device": (C.c_int, [C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
                                              C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                              _vp, _vp, _vp, _vp, _vp]),
+    "ldsr_pcr_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, C.POINTER(C.c_ubyte), C.c_int,
+                                 _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
     "ldsr_profile_enable": (None, [C.c_int]),
     "ldsr_profile_collect": (C.c_int, [_dp, _ip]),
     "ldsr_select_restart": (C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int]),
