@@ -54,6 +54,9 @@ __host__ __device__ constexpr long pair_tri_doubles(int PP, int QQ, int LPC = 32
 #ifndef LDSR_STEADY_PF2        // ... and of the strip reads in F2
 #define LDSR_STEADY_PF2 6
 #endif
+#ifndef LDSR_STEADY_REREAD_U   // steady sweeps: F2 rebuilds B u_t from the image's u values instead of the strip
+#define LDSR_STEADY_REREAD_U 1 // (padded p = 1: REREAD_U in em_pair_body_steady); 0: F1 stores it, F2 loads it (A/B builds)
+#endif
 #ifndef LDSR_LEAD_CLOSED_VAR    // LEAD pass 1: multipliers and variance offset of a lane's steps in closed form
 #define LDSR_LEAD_CLOSED_VAR 1
 #endif
@@ -1388,6 +1391,14 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
     // shorter ring) and the strip
     constexpr int PF = KP <= 2 ? LDSR_STEADY_PF : (KP <= 4 ? 2 : 1);
     constexpr int PF2 = LDSR_STEADY_PF2;
+    // B u_t between F1 and F2: through the wave's strip it costs the CU's LDS pipe a ds_write_b64 (~6 cycles)
+    // in F1 and a ds_read_b64 (2) in F2, 8 per step and wave.  Rebuilt in F2 from the image's own u values it
+    // costs one ds_read_b64 per input and the PP fma F1 already did; the lanes of an image read are 16 bytes
+    // apart, so lanes l and l + 16 of each 32-lane group meet on a bank: 2-way, 4 cycles per read (measured:
+    // 2.4 extra SQ_LDS_BANK_CONFLICT cycles per read, EXPERIMENTS.md R14.1).  4 PP < 8 for PP = 1 only; at
+    // PP = 2 the LDS cycles are the same and the two fma more lose 2..3 % (measured), so from there on the strip
+    // stays.  The rebuild is F1's own sequence, bu = 0, then bu = fma(B[p], u[p], bu): the same bits.
+    constexpr bool REREAD_U = LDSR_STEADY_REREAD_U != 0 && 4 * PP < 6 + 2;
     const int T = prm.T;
     const int P = 6 + prm.p + prm.q;
     PairEnv E;
@@ -1516,8 +1527,10 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
                 // The series image is read PF steps ahead through an explicit register ring pinned by
                 // scheduling barriers: left alone, the scheduler issued each ds_read_b128 right before
                 // its use (one read in flight, 35 ns exposed per read: the sweeps were LDS-latency bound).
-                // (the strip is free here: the steady sweeps have no h_t; J_t's registers stay unused, which
-                // is what makes room for the read-ahead rings at two waves per SIMD)
+                // (the steady sweeps have no h_t, so the wave's strip has room for B u_t -- but not for free:
+                // its store is 6 of F1's 14 LDS cycles per step, on a pipe the CU's eight waves share.  With one
+                // input, REREAD_U, F1 leaves the strip alone and F2 rebuilds B u_t from the image.  J_t's registers
+                // stay unused, which is what makes room for the read-ahead rings at two waves per SIMD)
                 double gv_[L];           // e_t, then g_t of this lane's steps
                 double al = 1.0, bl = 0.0, buLast = 0.0;
                 auto f1s = [&](int j, const double (&w)[2 * KP]) {
@@ -1527,7 +1540,8 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
 #pragma unroll
                     for (int p_ = 0; p_ < PP; p_++) bu = fma(th.B[p_], w[1 + p_], bu);
                     gv_[j] = e;
-                    if (j < L - 1) hs[j * 64] = bu; else buLast = bu;   // B u_t waits for F2 in the wave's LDS strip
+                    if (j == L - 1) buLast = bu;
+                    else if constexpr (!REREAD_U) hs[j * 64] = bu;      // B u_t waits for F2 in the wave's LDS strip
                     bl = fma(a, bl, fma(aK, e, bu));
                 };
                 {
@@ -1569,6 +1583,17 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
                 // (static schedule: dl^2 is summed only in the iterations whose likelihood is read, by a pass of
                 // its own ahead of F2 -- the same operations from the same entry state, the same bits)
                 constexpr bool LOD = !QUEUE;
+                // (REREAD_U) the u values of step j, one ds_read_b64 each, and B u_t from them as F1 builds it
+                auto ldu = [&](int j, double (&uv)[PP]) {
+#pragma unroll
+                    for (int p_ = 0; p_ < PP; p_++) uv[p_] = val(j, 1 + p_);
+                };
+                auto bu_of = [&](const double (&uv)[PP]) {
+                    double bu = 0.0;
+#pragma unroll
+                    for (int p_ = 0; p_ < PP; p_++) bu = fma(th.B[p_], uv[p_], bu);
+                    return bu;
+                };
                 if constexpr (LOD) {
                     if (need_lik) {
                         double Xl = Xq;
@@ -1579,7 +1604,15 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
                         };
                         if (body) {
 #pragma unroll
-                            for (int j = 0; j < L - 1; j++) f2l(j, hs[j * 64]);
+                            for (int j = 0; j < L - 1; j++) {
+                                if constexpr (REREAD_U) {
+                                    double uv[PP];
+                                    ldu(j, uv);
+                                    f2l(j, bu_of(uv));
+                                } else {
+                                    f2l(j, hs[j * 64]);
+                                }
+                            }
                         }
                         if (tail_s) f2l(L - 1, buLast);
                     }
@@ -1599,15 +1632,28 @@ __device__ __forceinline__ void em_pair_body_steady(const EmParams &prm, const d
                     Xq = Xq1;
                 };
                 if (body) {
-                    double U[PF2];
+                    if constexpr (REREAD_U) {
+                        double U[PF2][PP];       // the ring holds the u values read ahead
 #pragma unroll
-                    for (int d = 0; d < PF2; d++) U[d] = hs[d * 64];
-                    __builtin_amdgcn_sched_barrier(LDSR_STEADY_SBMASK);
-#pragma unroll
-                    for (int j = 0; j < L - 1; j++) {
-                        f2s(j, U[j % PF2]);
-                        if (j + PF2 < L - 1) U[j % PF2] = hs[(j + PF2) * 64];
+                        for (int d = 0; d < PF2; d++) ldu(d, U[d]);
                         __builtin_amdgcn_sched_barrier(LDSR_STEADY_SBMASK);
+#pragma unroll
+                        for (int j = 0; j < L - 1; j++) {
+                            f2s(j, bu_of(U[j % PF2]));
+                            if (j + PF2 < L - 1) ldu(j + PF2, U[j % PF2]);
+                            __builtin_amdgcn_sched_barrier(LDSR_STEADY_SBMASK);
+                        }
+                    } else {
+                        double U[PF2];
+#pragma unroll
+                        for (int d = 0; d < PF2; d++) U[d] = hs[d * 64];
+                        __builtin_amdgcn_sched_barrier(LDSR_STEADY_SBMASK);
+#pragma unroll
+                        for (int j = 0; j < L - 1; j++) {
+                            f2s(j, U[j % PF2]);
+                            if (j + PF2 < L - 1) U[j % PF2] = hs[(j + PF2) * 64];
+                            __builtin_amdgcn_sched_barrier(LDSR_STEADY_SBMASK);
+                        }
                     }
                 }
                 if (tail_s) f2s(L - 1, buLast);
