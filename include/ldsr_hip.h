@@ -369,6 +369,19 @@ int ldsr_bfgs_update_batch(int device, int n_series, int T, int p, int q, const 
 int ldsr_plg_extent_check(int kernel, int n_series, int T, int p, int q, int has_u, int has_v, int shared_uv,
                           const int *cell_offsets, int with_grad, long strip_short, long out_shift);
 
+/* Test hooks of the arenas' guard mode (LDSR_ARENA_GUARD=1 in the environment when the library is loaded; off, and
+ * free, by default).  In that mode every buffer a host-pointer entry carves out of its arena is followed by a band of
+ * at least 256 bytes and the block by one of 64 KiB, the whole block is filled with 0xFF before the entry uploads
+ * anything, and when the call's lease ends the bands are read back: every band with a changed byte is one violation.
+ *   ldsr_arena_guard_report    number of violations since the last report; their descriptions, one per line (entry,
+ *                              carve index, offsets, byte count), go into buf (may be NULL)
+ *   ldsr_arena_guard_selftest  leases an arena, carves two buffers, sets ONE byte of the band between them with
+ *                              hipMemset from the host, and releases: the next report counts exactly one violation,
+ *                              "band behind carve 0".  Launches no kernel and touches only memory the arena owns.
+ *                              LDSR_EINVAL when the mode is off. */
+int ldsr_arena_guard_report(char *buf, size_t len);
+int ldsr_arena_guard_selftest(int device);
+
 /* Stochastic replicates: one_LDS_rep / LDS_rep (R/stochastics.R:18-63) for n_models thetas x
  * num_reps replicates of T steps,
  *   x_1 ~ N(0, V1), x_{t+1} = A x_t + B u_t + q_t, y_t = C x_t + D v_t + r_t, q_t ~ N(0, Q), r_t ~ N(0, R),

@@ -67,6 +67,8 @@ SIGNATURES = {
                                          C.c_int, _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ldsr_plg_extent_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         _ip, C.c_int, C.c_long, C.c_long]),
+    "ldsr_arena_guard_report": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "ldsr_arena_guard_selftest": (C.c_int, [C.c_int]),
     "ldsr_simulate_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp,
                                       _dp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _dp, _dp, _dp, _dp]),
     "ldsr_simulate_draw_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int,

@@ -114,7 +114,7 @@ extern "C" int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q
     const size_t out_bytes = c.o - o_f;
     const size_t strip_bytes = grad ? ssq_strip_bytes(n_cells, T) : 0;
     const size_t o_strip = c.take(strip_bytes);
-    rc = arena_reserve(A, c.o, in_bytes + align256(out_bytes));
+    rc = arena_reserve(A, c, in_bytes + align256(out_bytes), "ldsr_ssq_grad_batch");
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
     U.stage(A);
@@ -142,13 +142,13 @@ struct BfgsCall {
     WsLayout L;
     size_t nT, o_lb, o_ub, o_off, in_bytes, o_win, o_thw, o_vw, sel_bytes, o_par, o_val, o_nit, o_nev, o_st, cell_bytes,
            o_lik, o_X, o_Y, o_V, o_J, o_fst, fit_bytes, o_fsoc, o_fth, strip_bytes, o_strip, o_ws, total;
+    Carver c;
     BfgsCall(const SeriesUpload &series, const int *cell_offsets, const double *par0, bool update_)
         : U(series), update(update_) {
         const int n_series = U.n_series, T = U.T;
         n_cells = cell_offsets[n_series]; P = 6 + U.p + U.q;
         L = ws_layout(n_series, T, ldsr_pad_dim(U.p), ldsr_pad_dim(U.q), U.shared_uv, n_series, LDSR_ALGO_SCAN, 1);
         nT = (size_t)n_series * T;
-        Carver c;
         U.carve(c, cell_offsets, par0);
         o_lb = c.take(sizeof(double) * (size_t)P);
         o_ub = c.take(sizeof(double) * (size_t)P);
@@ -235,7 +235,8 @@ static int run_bfgs(bool update, double lambda, int device, int n_series, int T,
     SeriesUpload &U = B.U;
     const size_t nT = B.nT;
     const bool want_cells = par_all || value_all || n_iter_all || n_eval_all || status_all;
-    rc = arena_reserve(A, B.total, B.in_bytes + align256(B.sel_bytes) + align256(std::max(B.cell_bytes, B.fit_bytes)));
+    rc = arena_reserve(A, B.c, B.in_bytes + align256(B.sel_bytes) + align256(std::max(B.cell_bytes, B.fit_bytes)),
+                       update ? "ldsr_bfgs_update_batch" : "ldsr_bfgs_batch");
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
     U.stage(A);
@@ -360,9 +361,9 @@ struct PlGradCall {
     SeriesUpload U;
     int n_cells, P;
     size_t in_bytes, o_f, o_g, g_bytes, out_bytes, o_strip, strip_bytes, total;
+    Carver c;
     PlGradCall(const SeriesUpload &series, const int *cell_offsets, const double *theta, bool grad) : U(series) {
         n_cells = cell_offsets[U.n_series]; P = 6 + U.p + U.q;
-        Carver c;
         U.carve(c, cell_offsets, theta);
         in_bytes = c.o;
         o_f = c.take(sizeof(double) * (size_t)n_cells);
@@ -405,7 +406,7 @@ extern "C" int ldsr_pl_grad_batch(int device, int n_series, int T, int p, int q,
     if (rc) return rc;
     Arena *A = lease.a;
     PlGradCall call(SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets, theta, grad != nullptr);
-    rc = arena_reserve(A, call.total, call.in_bytes + align256(call.out_bytes));
+    rc = arena_reserve(A, call.c, call.in_bytes + align256(call.out_bytes), "ldsr_pl_grad_batch");
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
     call.U.stage(A);

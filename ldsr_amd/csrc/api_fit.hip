@@ -40,7 +40,8 @@ struct FitCall {
         small_out = c.o - o_lik;
         const size_t o_X = c.take(xv_bytes), o_V = c.take(xv_bytes), o_Y = c.take(yj_bytes), o_J = c.take(yj_bytes);
         const size_t o_ws = c.take(L.total);
-        rc = arena_reserve(A, c.o, in_bytes + align256(small_out));
+        static const char *const entry[] = {"ldsr_smooth_batch", "ldsr_propagate_batch", "ldsr_mstep_batch", "ldsr_penalized_lik_batch"};
+        rc = arena_reserve(A, c, in_bytes + align256(small_out), entry[kind]);
         if (rc) return rc;
         char *dev = A->dev;
         pout = A->pin + in_bytes;

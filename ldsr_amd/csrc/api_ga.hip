@@ -88,7 +88,7 @@ extern "C" int ldsr_ga_batch(int device, int n_series, int T, int p, int q, cons
         o_V = c.take(sizeof(double) * strip_cells * T);
         o_ws = c.take(L.total);
         const size_t sc_bytes = align256(2 * sizeof(int) * (size_t)n_series);      // (n_obs, status) of every series
-        rc = arena_reserve(A, c.o, in_bytes + align256(out_bytes) + sc_bytes);
+        rc = arena_reserve(A, c, in_bytes + align256(out_bytes) + sc_bytes, "ldsr_ga_batch");
         if (rc) return rc;
         dev = A->dev; pin = A->pin;
         U.stage(A);

@@ -75,7 +75,7 @@ struct WinLayout {
 };
 static WinLayout win_layout(int n, int P, int T, int niter) {
     WinLayout W;
-    Carver c;
+    Carver c(true);         // (a layout inside one buffer of the slice's block)
     W.ser = c.take(sizeof(int) * n);
     W.theta0 = c.take(sizeof(double) * n * P);
     W.st = c.take(sizeof(int) * n);
@@ -172,13 +172,12 @@ static int slice_run(Slice &S) {
     const WinLayout W = win_layout(std::max(S.max_winners, 1), P, T, S.niter);
     S.d_w = c.take(S.max_winners > 0 ? W.total : 0);
     S.w_bytes = S.max_winners > 0 ? W.total : 0;
-    const size_t dev_total = c.o;
     // pinned: inputs, outputs, phase-2 block (same relative layouts as on the device)
     S.p_in = 0;
     S.p_out = align256(S.in_bytes);
     S.p_w = S.p_out + align256(S.out_bytes);
     const size_t pin_total = S.p_w + S.w_bytes;
-    rc = arena_reserve(A, dev_total, pin_total);
+    rc = arena_reserve(A, c, pin_total, "the EM slice (ldsr_em_batch / _multi / ldsr_em_restart_grid / _groups)");
     if (rc) return rc;
 
     // stage inputs

@@ -60,7 +60,7 @@ extern "C" int ldsr_pcr_batch(int device, int n_members, int n, const int *k, co
     const size_t o_coef = c.take(coef ? sizeof(double) * cells * PCR_COEF_STRIDE : 0);
     const size_t o_sig = c.take(sigma ? sizeof(double) * cells : 0);
     const size_t o_df = c.take(df ? sizeof(int) * cells : 0), o_st = c.take(sizeof(int) * cells);
-    rc = arena_reserve(A, c.o, in_bytes);
+    rc = arena_reserve(A, c, in_bytes, "ldsr_pcr_batch");
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
     memcpy(pin + o_k, k, b_k);

@@ -75,7 +75,7 @@ extern "C" int ldsr_simulate_batch(int device, int n_models, int T, int p, int q
     const size_t o_X = c.take(simX ? sizeof(double) * n_out : 0);
     const size_t o_Y = c.take(simY ? sizeof(double) * n_out : 0);
     const size_t o_Q = c.take(simQ ? sizeof(double) * n_out : 0);
-    rc = arena_reserve(A, c.o, in_bytes);
+    rc = arena_reserve(A, c, in_bytes, "ldsr_simulate_batch");
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
     memcpy(pin + o_th, theta, sizeof(double) * (size_t)n_models * P);

@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <string>
+#include <vector>
 
 #include "../../include/ldsr_hip.h"
 
@@ -52,12 +53,28 @@ int stage_h2d_async(int device, hipStream_t stream, void *dst, const void *src, 
 // One arena = one device block + one pinned host block (both grow-only) + one non-blocking
 // stream.  A call leases a free arena of its device (or creates one), so concurrent callers never
 // share buffers, and repeated calls of the same shape do no hipMalloc / hipFree at all.
+// Guard mode (LDSR_ARENA_GUARD=1 in the environment, read once; a debug mode, off by default): a Carver leaves a
+// band behind every buffer, arena_reserve adds a tail band and fills the whole device block (and the pinned block,
+// which the entries' one upload copies over the bands between their inputs) with 0xFF before the entry uploads
+// anything, and the end of the lease synchronises the stream, reads the bands back and records every changed byte
+// for ldsr_arena_guard_report.  Off: Carver::take returns the offsets it always did and no call path does more.
+bool arena_guard_on();
+constexpr size_t kGuardBand = 256;              // behind every buffer, on top of its alignment slack
+constexpr size_t kGuardTail = 64 * 1024;        // behind the last one
+
+struct GuardBand {
+    size_t begin, end;      // arena offsets: [end of the buffer's bytes, start of the next buffer)
+};
+
 struct Arena {
     int device = -1;
     hipStream_t stream = nullptr;
     char *dev = nullptr, *pin = nullptr;
     size_t dev_cap = 0, pin_cap = 0;
     bool busy = false;
+    // guard mode: the bands of the lease's reserve (the last one is the tail band) and the entry that carved them
+    std::vector<GuardBand> bands;
+    const char *entry = nullptr;
 };
 
 int arena_acquire(int device, Arena **out);
@@ -68,17 +85,26 @@ struct ArenaLease {     // releases on scope exit
     ~ArenaLease() { arena_release(a); }
 };
 
-int arena_reserve(Arena *a, size_t dev_bytes, size_t pin_bytes);
-
-// bump allocator over an arena block: first pass sizes, second pass hands out pointers
+// bump allocator over an arena block: first pass sizes, second pass hands out pointers.  sub: a layout inside one
+// buffer of another Carver (the EM workspace, the restart grid's winners' block): never banded.
 struct Carver {
     size_t o = 0;
+    bool guard;
+    std::vector<GuardBand> bands;       // (guard mode only)
+    explicit Carver(bool sub = false) : guard(!sub && arena_guard_on()) {}
     size_t take(size_t bytes) {
-        const size_t r = o;
-        o = align256(o + (bytes ? bytes : 8));
+        const size_t r = o, n = bytes ? bytes : 8;
+        o = align256(o + n);
+        if (guard) {
+            o += kGuardBand;
+            bands.push_back(GuardBand{r + n, o});
+        }
         return r;
     }
 };
+
+// room for what `c` carved (guard mode: and its bands, checked when the lease ends under the name `entry`)
+int arena_reserve(Arena *a, const Carver &c, size_t pin_bytes, const char *entry);
 
 // ---- argument checks shared by the entries -----------------------------------------------------
 int check_common(int n_series, int T, int p, int q, const double *y, const int *cell_offsets);

@@ -7,6 +7,8 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -264,13 +266,103 @@ int arena_acquire(int device, Arena **out) {
     return LDSR_OK;
 }
 
+// ---- guard mode (host_runtime.h) ---------------------------------------------------------------------
+bool arena_guard_on() {
+    static const bool on = [] { const char *e = getenv("LDSR_ARENA_GUARD"); return e && e[0] == '1'; }();
+    return on;
+}
+
+static std::mutex g_guard_mu;
+static std::vector<std::string> g_guard_hits;      // violations since the last ldsr_arena_guard_report
+
+static void guard_record(const std::string &msg) {
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    g_guard_hits.push_back(msg);
+}
+
+// the end of a lease (or a second reserve inside one): wait for the arena's stream, read the block back, look at
+// every band
+static void guard_check(Arena *a) {
+    if (a->bands.empty()) return;
+    std::vector<GuardBand> bands;
+    bands.swap(a->bands);
+    const std::string entry = a->entry ? a->entry : "?";
+    const size_t used = bands.back().end;
+    std::vector<unsigned char> host(used);
+    hipError_t e = hipSetDevice(a->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
+    if (e == hipSuccess) e = hipMemcpy(host.data(), a->dev, used, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        guard_record(entry + ": the bands could not be read back: " + hipGetErrorString(e));
+        return;
+    }
+    for (size_t i = 0; i < bands.size(); i++) {
+        size_t n = 0, first = 0, last = 0;
+        for (size_t o = bands[i].begin; o < bands[i].end; o++)
+            if (host[o] != 0xFF) {
+                if (!n++) first = o;
+                last = o;
+            }
+        if (!n) continue;
+        char where[64], msg[256];
+        if (i + 1 == bands.size()) snprintf(where, sizeof(where), "tail band");
+        else snprintf(where, sizeof(where), "band behind carve %zu", i);
+        snprintf(msg, sizeof(msg), "%s: %s (arena offsets %zu..%zu): %zu byte(s) changed, first at band offset %zu, last at %zu",
+                 entry.c_str(), where, bands[i].begin, bands[i].end, n, first - bands[i].begin, last - bands[i].begin);
+        guard_record(msg);
+    }
+}
+
+extern "C" int ldsr_arena_guard_report(char *buf, size_t len) {
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    std::string s;
+    for (const std::string &h : g_guard_hits) s += h + "\n";
+    if (buf && len) snprintf(buf, len, "%s", s.c_str());
+    const int n = (int)g_guard_hits.size();
+    g_guard_hits.clear();
+    return n;
+}
+
 void arena_release(Arena *a) {
     if (!a) return;
+    guard_check(a);
     std::lock_guard<std::mutex> lk(g_arena_mu);
     a->busy = false;
 }
 
-int arena_reserve(Arena *a, size_t dev_bytes, size_t pin_bytes) {
+static int arena_reserve(Arena *a, size_t dev_bytes, size_t pin_bytes);
+
+int arena_reserve(Arena *a, const Carver &c, size_t pin_bytes, const char *entry) {
+    if (!c.guard) return arena_reserve(a, c.o, pin_bytes);
+    guard_check(a);
+    const int rc = arena_reserve(a, c.o + kGuardTail, pin_bytes);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(a->dev, 0xFF, a->dev_cap, a->stream));
+    if (a->pin_cap) memset(a->pin, 0xFF, a->pin_cap);
+    a->bands = c.bands;
+    a->bands.push_back(GuardBand{c.o, c.o + kGuardTail});
+    a->entry = entry;
+    return LDSR_OK;
+}
+
+// Test hook: one lease with two buffers, one byte of the band between them set from the host (no kernel runs, and
+// only the arena's own memory is touched); the next report counts exactly that.
+extern "C" int ldsr_arena_guard_selftest(int device) {
+    if (!arena_guard_on()) return fail(LDSR_EINVAL, "LDSR_ARENA_GUARD=1 is not set: the arenas have no bands");
+    ArenaLease lease;
+    int rc = arena_acquire(device, &lease.a);
+    if (rc) return rc;
+    Carver c;
+    c.take(1000);
+    c.take(1000);
+    rc = arena_reserve(lease.a, c, 0, "ldsr_arena_guard_selftest");
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(lease.a->stream));
+    HIPCHK(hipMemset(lease.a->dev + c.bands[0].begin + 3, 0, 1));
+    return LDSR_OK;
+}
+
+static int arena_reserve(Arena *a, size_t dev_bytes, size_t pin_bytes) {
     if (dev_bytes > a->dev_cap) {
         HIPCHK(hipStreamSynchronize(a->stream));
         if (a->dev) (void)hipFree(a->dev);
