@@ -1326,6 +1326,492 @@ __device__ __forceinline__ bool pair_need_lik(const PairEnv &E, const PairCarry<
                       (E.abort != nullptr && ((cs.wit + 1) & 63) == 0)) != 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The generic iteration of the steady members' G phase, on SUB-CHUNKS (LDSR_G_SUBCHUNK; 0: the parent's form,
+// pair_generic_sweeps on whole chunks, for A/B builds).
+//
+// A chunk of L steps is two sub-chunks: `a` = its first LA = ceil(L/2) steps, `b` = the rest (LB = L - LA, the
+// last of them the predicated step L-1).  F1 forms the composite of each; the chunk's is b o a (one structured
+// product, renormalised).  F2 of `b` starts from a's composite applied to the chunk's (projective) entry state,
+// not from where F2 of `a` ended; the reverse side likewise: the chunk's reverse composite is a's then b's, and
+// B2 of `a` starts from b's reverse composite applied to the value behind the chunk.  The M-step sums of a lane
+// are sum(a) + sum(b), each accumulated from zero; lik's two terms likewise.
+// Defined like this a sub-chunk's arithmetic needs nothing of the other one but its composites, so ONE body
+// (gsub_f1 / gsub_f2 / gsub_b2, explicit fma / mul) serves two drivers that give the same bits:
+//   32 lanes per cell (both cells of the wave slow): a lane runs the body for `a`, then for `b`;
+//   64 lanes for ONE cell (its partner waits): lane vl of half 0 runs `a` of chunk vl, lane vl of half 1 `b`, the
+//   composites and sums are exchanged with v_permlane32_swap, the 32-lane scans run redundantly in both halves.
+// What differs between a lane's sub-chunks is data: where its steps are in the image, how many it has, whether
+// step T-1 is its last.
+#ifndef LDSR_G_SUBCHUNK
+#define LDSR_G_SUBCHUNK 1
+#endif
+#ifndef LDSR_G_WIDTH           // 0: the width is chosen per G iteration.  32 / 64: that driver alone (listings only: tools/loop_mix.py
+#define LDSR_G_WIDTH 0         // then counts one driver's iteration; 64 lanes for two slow cells compute nonsense)
+#endif
+// Which steady members take it: those with at most two 16-byte pairs per step (padded (p, q) = (1, 1), (1, 2),
+// (2, 1)).  With wider inputs theta, the sums of two sub-chunks and the image's 128-bit reads leave the allocator
+// no room: every such member had scratch reloads inside the G loop (three to sixteen blocks, mostly the work-queue
+// form), where the parent's has none.  They keep the parent's generic iteration.
+__host__ __device__ constexpr bool pair_gsub(int PP, int QQ) { return LDSR_G_SUBCHUNK != 0 && (1 + PP + QQ + 1) / 2 <= 2; }
+__host__ __device__ constexpr int gsub_la(int L) { return (L + 1) / 2; }
+__host__ __device__ constexpr int gsub_lb(int L) { return L - (L + 1) / 2; }
+
+// iteration constants of a cell (the dense step block scaled by c = 2^-k: pair_generic_sweeps F1)
+struct GsubConst {
+    double A, C, Q, R, A2, C2, C2R, ACR, c, cinv, al_, Q_, C2R_, A_;
+};
+// this lane's sub-chunk
+struct GsubLane {
+    const double *yp;        // image: the full pairs of its local step 0 ...
+    const double *yo[2];     // ... and the odd value's pair of an even / odd local step
+    double *hp;              // strip column, row of its local step 0
+    int ns;                  // its steps: LA, or LB-1 / LB
+    bool fin;                // step T-1 is its last step
+};
+template <int PP, int QQ>
+struct GsubOut {             // what a sub-chunk's sweeps leave in its lane
+    double aSyx, aTx1x, aPall, likq, lsp, tLv, X0v, V0v;
+    double aSxv[QQ], aTx1u[PP], aTux[PP];
+    int sneg;
+};
+
+template <int PP, int QQ, int L>
+__device__ __forceinline__ GsubLane gsub_lane(const double *ys, double *hs, int vl, int sub, int hrow, bool tail, bool last) {
+    constexpr int LPC = 32, KV = img_values(PP, QQ), LA = gsub_la(L), LB = gsub_lb(L);
+    constexpr int dp = img_off(LA, 0, KV, LPC, L) - img_off(0, 0, KV, LPC, L);
+    constexpr int de = img_off(LA, KV - 1, KV, LPC, L) - img_off(0, KV - 1, KV, LPC, L);
+    constexpr int dod = img_off(LA + 1, KV - 1, KV, LPC, L) - img_off(1, KV - 1, KV, LPC, L);
+    GsubLane sb;
+    const double *y0 = ys + vl * 2;
+    sb.yp = y0 + (sub ? dp : 0);
+    sb.yo[0] = y0 + (sub ? de : 0);
+    sb.yo[1] = y0 + (sub ? dod : 0);
+    sb.hp = hs + hrow * 64;
+    sb.ns = sub ? LB - 1 + (tail ? 1 : 0) : LA;
+    sb.fin = sub != 0 && last;
+    return sb;
+}
+
+template <int PP, int QQ, int L>
+__device__ __forceinline__ GsubConst gsub_const(const Theta<PP, QQ> &th) {
+    GsubConst k;
+    k.A = th.A; k.C = th.C; k.Q = th.Q; k.R = th.R;
+    k.A2 = k.A * k.A; k.C2 = k.C * k.C;
+    const double rR = fast_rcp(k.R);
+    k.C2R = k.C2 * rR; k.ACR = k.A * k.C * rR;
+    const double alpha = fma(k.Q, k.C2R, k.A2);
+    const double mx = fmax(alpha, 1.0);
+    const int ke = -__builtin_amdgcn_frexp_exp(mx);
+    k.c = __builtin_amdgcn_ldexp(1.0, ke); k.cinv = __builtin_amdgcn_ldexp(1.0, -ke);
+    k.al_ = alpha * k.c; k.Q_ = k.Q * k.c; k.C2R_ = k.C2R * k.c; k.A_ = k.A * k.c;
+    return k;
+}
+
+// ... and the powers of the scaled dense 2x2 step block Bm' (pair_generic_sweeps F1) a sub-chunk can need:
+// pw[0] = Bm'^(LB-1), pw[1] = Bm'^LB, pw[2] = Bm'^LA where LA > LB.  (Formed behind F1's row recursions, not held
+// through them.)
+template <int L>
+__device__ __forceinline__ void gsub_powers(const GsubConst &k, double (&pw)[3][4]) {
+    constexpr int LA = gsub_la(L), LB = gsub_lb(L);
+    double p00 = k.al_, p01 = k.Q_, p10 = k.C2R_, p11 = k.c;      // running square Bm'^(2^bit)
+    double q00 = 1.0, q01 = 0.0, q10 = 0.0, q11 = 1.0;            // Bm'^(LB-1)
+    bool have = false;
+    constexpr int n1 = LB - 1;
+#pragma unroll
+    for (int bit = 0; (1 << bit) <= n1; bit++) {
+        if (n1 & (1 << bit)) {
+            if (!have) { q00 = p00; q01 = p01; q10 = p10; q11 = p11; have = true; }
+            else {
+                const double t00 = fma(q00, p00, q01 * p10), t01 = fma(q00, p01, q01 * p11);
+                const double t10 = fma(q10, p00, q11 * p10), t11 = fma(q10, p01, q11 * p11);
+                q00 = t00; q01 = t01; q10 = t10; q11 = t11;
+            }
+        }
+        if ((2 << bit) <= n1) {
+            const double t00 = fma(p00, p00, p01 * p10), t01 = fma(p00, p01, p01 * p11);
+            const double t10 = fma(p10, p00, p11 * p10), t11 = fma(p10, p01, p11 * p11);
+            p00 = t00; p01 = t01; p10 = t10; p11 = t11;
+        }
+    }
+    pw[0][0] = q00; pw[0][1] = q01; pw[0][2] = q10; pw[0][3] = q11;
+#pragma unroll
+    for (int m = 1; m < (LA > LB ? 3 : 2); m++) {      // ... times Bm'
+        pw[m][0] = fma(pw[m - 1][0], k.al_, pw[m - 1][1] * k.C2R_); pw[m][1] = fma(pw[m - 1][0], k.Q_, pw[m - 1][1] * k.c);
+        pw[m][2] = fma(pw[m - 1][2], k.al_, pw[m - 1][3] * k.C2R_); pw[m][3] = fma(pw[m - 1][2], k.Q_, pw[m - 1][3] * k.c);
+    }
+}
+
+// F1 of a sub-chunk: the third row of its composite (gsub_f1_fin adds the 2x2 block: a power of Bm', not held
+// through the next sub-chunk's recursion); e_t is left for F2 in the g_t slots.  (B u_t is not: F2 rebuilds it from
+// the image with F1's own sequence, bu = 0, bu = fma(B[p], u[p], bu) -- the same bits for a ds_read_b64 and an fma
+// per input and step.  Handed over in the J_t slots, as pair_generic_sweeps does, the 4 LA registers it holds from
+// F1 to the end of both F2 are what two sub-chunks' composites and sums no longer leave room for.)
+struct GsubRow { double ra, rb, r22; };
+template <int PP, int QQ, int L>
+__device__ __forceinline__ GsubRow gsub_f1(const GsubConst &k, const Theta<PP, QQ> &th, const GsubLane &sb, bool act,
+                                           double (&gv)[gsub_la(L)]) {
+    constexpr int LPC = 32, KV = img_values(PP, QQ), KH2 = 2 * (KV / 2), LA = gsub_la(L), LB = gsub_lb(L);
+    auto val = [&](int i, int v) -> double {
+        return (v < KH2 ? sb.yp : sb.yo[i & 1])[img_off(i, v, KV, LPC, L)];
+    };
+    double ra = 0.0, rb = 0.0, rcc = k.c;
+    if (act) {
+        auto row = [&](int i) {
+            double e = val(i, 0), bu = 0.0;
+#pragma unroll
+            for (int q_ = 0; q_ < QQ; q_++) e = fma(-th.D[q_], val(i, 1 + PP + q_), e);
+#pragma unroll
+            for (int p_ = 0; p_ < PP; p_++) bu = fma(th.B[p_], val(i, 1 + p_), bu);
+            gv[i] = e;
+            const double s20 = fma(bu, k.C2R, k.ACR * e);
+            const double na = fma(ra, k.al_, fma(rb, k.C2R_, rcc * s20));
+            rb = fma(rb, k.c, fma(ra, k.Q_, rcc * bu));
+            ra = na;
+            rcc *= k.A_;
+        };
+#pragma unroll
+        for (int i = LA - 1; i >= 0; i--)
+            if (i < LB - 1 || i < sb.ns) row(i);
+    }
+    GsubRow r;
+    r.ra = ra; r.rb = rb; r.r22 = rcc * k.cinv;
+    return r;
+}
+template <int L>
+__device__ __forceinline__ PMat gsub_f1_fin(const GsubConst &k, const GsubRow &r, int ns, bool act) {
+    constexpr int LA = gsub_la(L), LB = gsub_lb(L);
+    PMat M;
+    M.m00 = 1.0; M.m01 = 0.0; M.m10 = 0.0; M.m11 = 1.0; M.m20 = 0.0; M.m21 = 0.0; M.m22 = 1.0;
+    if (act) {
+        const int m = ns - (LB - 1);          // 0, 1 (or 2: LA = LB + 1)
+        double pw[3][4];
+        gsub_powers<L>(k, pw);
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const double pv = m == 0 ? pw[0][v] : ((m == 1 || LA == LB) ? pw[1][v] : pw[2][v]);
+            if (v == 0) M.m00 = pv; else if (v == 1) M.m01 = pv; else if (v == 2) M.m10 = pv; else M.m11 = pv;
+        }
+        M.m20 = r.ra; M.m21 = r.rb; M.m22 = r.r22;
+        prenorm(M);
+    }
+    return M;
+}
+
+// chunk composite b o a, forward scan over the cell's 32 lanes, the entry states of both sub-chunks
+__device__ __forceinline__ void gsub_entry(const PMat &Ma, const PMat &Mb, double x_in, double v_in, int vl,
+                                           double &Xa, double &Va, double &Xb, double &Vb) {
+    PMat M = pmul(Mb, Ma);
+    prenorm(M);
+    M = pmul(M, pdpp<DPP_ROW_SHR(1), 0xF>(M));
+    M = pmul(M, pdpp<DPP_ROW_SHR(2), 0xF>(M));
+    M = pmul(M, pdpp<DPP_ROW_SHR(4), 0xF>(M));
+    prenorm(M);
+    M = pmul(M, pdpp<DPP_ROW_SHR(8), 0xF>(M));
+    M = pmul(M, pdpp<DPP_ROW_BCAST15, 0xA>(M));
+    const double n_in = v_in, d_in = 1.0;
+    double n_e = fma(M.m00, n_in, M.m01 * d_in);
+    double d_e = fma(M.m10, n_in, M.m11 * d_in);
+    double x_e = fma(M.m20, n_in, fma(M.m21, d_in, M.m22 * x_in));
+    n_e = dppd<DPP_WAVE_SHR1, 0xF>(n_in, n_e);
+    d_e = dppd<DPP_WAVE_SHR1, 0xF>(d_in, d_e);
+    x_e = dppd<DPP_WAVE_SHR1, 0xF>(x_in, x_e);
+    if (vl == 0) { n_e = n_in; d_e = d_in; x_e = x_in; }
+    {
+        const double rd = fast_rcp(d_e);
+        Va = n_e * rd;
+        Xa = x_e * rd;
+    }
+    {
+        const double n_b = fma(Ma.m00, n_e, Ma.m01 * d_e);
+        const double d_b = fma(Ma.m10, n_e, Ma.m11 * d_e);
+        const double x_b = fma(Ma.m20, n_e, fma(Ma.m21, d_e, Ma.m22 * x_e));
+        const double rd = fast_rcp(d_b);
+        Vb = n_b * rd;
+        Xb = x_b * rd;
+    }
+}
+
+// F2 of a sub-chunk from its entry state (pair_generic_sweeps' F2, DENSE): J_t, g_t stay in registers, h_t goes to
+// the strip (HR: the local step whose h has no row there and stays in `hreg`), the reverse composite (Pi, G, H)
+// of the sub-chunk is accumulated on the way.  LIKOD: see pair_generic_sweeps.
+template <int PP, int QQ, int L, bool LIKOD, int HR>
+__device__ __forceinline__ void gsub_f2(const GsubConst &k, const Theta<PP, QQ> &th, const GsubLane &sb, bool act, bool need_lik, double Xp, double Vp,
+                                        double (&gv)[gsub_la(L)], double (&Jv)[gsub_la(L)], double &hreg,
+                                        double &Pi, double &G, double &H, GsubOut<PP, QQ> &o) {
+    constexpr int LPC = 32, KV = img_values(PP, QQ), KH2 = 2 * (KV / 2), LA = gsub_la(L), LB = gsub_lb(L);
+    const double A = k.A, C = k.C, Q = k.Q, R = k.R, A2 = k.A2, C2 = k.C2;
+    auto bu_at = [&](int i) {
+        double bu = 0.0;
+#pragma unroll
+        for (int p_ = 0; p_ < PP; p_++)
+            bu = fma(th.B[p_], (1 + p_ < KH2 ? sb.yp : sb.yo[i & 1])[img_off(i, 1 + p_, KV, LPC, L)], bu);
+        return bu;
+    };
+    double sprod = 1.0, Xu = 0.0, Vu = 0.0, likq = 0.0, lsp = 0.0;
+    int sexp = 0, sneg = 0;
+    double sg = fma(C2, Vp, R);
+    double r0 = fast_rcp(sg);
+    Pi = 1.0; G = 0.0; H = 0.0;
+    if constexpr (LIKOD) {
+        if (need_lik) {
+            if (act) {
+                double Xl = Xp, Vl = Vp, sgl = sg, rl = r0;
+                auto f2l = [&](int i) {
+                    const double e = gv[i], bu = bu_at(i);
+                    sprod *= sgl;
+                    sneg |= __double2hiint(sgl);
+                    if ((i & 7) == 7) {
+                        sexp += __builtin_amdgcn_frexp_exp(sprod);
+                        sprod = __builtin_amdgcn_frexp_mant(sprod);
+                    }
+                    const double w = Vl * rl;
+                    const double K = C * w;                    // src/EM.cpp:86
+                    const double Vul = R * w;                  // :88
+                    const double dl = fma(-C, Xl, e);
+                    const double Xul = fma(K, dl, Xl);         // :87
+                    likq = fma(dl * rl, dl, likq);             // :122
+                    Vl = fma(A2, Vul, Q);                      // :76
+                    Xl = fma(A, Xul, bu);                      // :74
+                    sgl = fma(C2, Vl, R);
+                    rl = Vl * fast_rcp(sgl * Vl);
+                };
+#pragma unroll
+                for (int i = 0; i < LA; i++)
+                    if (i < LB - 1 || i < sb.ns) f2l(i);
+            }
+            lsp = fma((double)sexp, 0.69314718055994530942, log_pos(sprod));
+        }
+    }
+    auto f2 = [&](int i) {
+        const double e = gv[i], bu = bu_at(i);     // e_t left there by F1
+        if constexpr (!LIKOD) {
+            sprod *= sg;
+            sneg |= __double2hiint(sg);
+            if ((i & 7) == 7) {
+                sexp += __builtin_amdgcn_frexp_exp(sprod);
+                sprod = __builtin_amdgcn_frexp_mant(sprod);
+            }
+        }
+        const double w = Vp * r0;
+        const double K = C * w;                    // src/EM.cpp:86
+        Vu = R * w;                                // :88
+        const double dl = fma(-C, Xp, e);
+        Xu = fma(K, dl, Xp);                       // :87
+        if constexpr (!LIKOD) likq = fma(dl * r0, dl, likq);   // :122
+        const double Vp1 = fma(A2, Vu, Q);         // :76
+        const double Xp1 = fma(A, Xu, bu);         // :74
+        sg = fma(C2, Vp1, R);
+        const double z = fast_rcp(sg * Vp1);
+        const double rp1 = sg * z;
+        r0 = Vp1 * z;
+        const double AVu = A * Vu;
+        double J = AVu * rp1;                      // :100
+        double g = fma(-J, Xp1, Xu);
+        double h = fma(-J, AVu, Vu);
+        if (i >= LB - 2) {
+            // step T-1 starts the backward recursion: J = 0, g = Xu, h = Vu, zero terminal value
+            const bool fin = sb.fin && i == sb.ns - 1;
+            J = fin ? 0.0 : J;
+            g = fin ? Xu : g;
+            h = fin ? Vu : h;
+        }
+        Jv[i] = J; gv[i] = g;
+        if (i == HR) hreg = h; else sb.hp[i * 64] = h;
+        G = fma(Pi, g, G);
+        H = fma(Pi * Pi, h, H);
+        Pi *= J;
+        Xp = Xp1;
+        Vp = Vp1;
+        if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+    };
+    if (act) {
+#pragma unroll
+        for (int i = 0; i < LA; i++)
+            if (i < LB - 1 || i < sb.ns) f2(i);
+    }
+    o.tLv = fma(Xu, Xu, Vu);                       // Xs^2 + Vs at T-1 (where sb.fin)
+    if constexpr (!LIKOD) lsp = fma((double)sexp, 0.69314718055994530942, log_pos(sprod));
+    o.likq = likq; o.lsp = lsp; o.sneg = sneg;
+}
+
+// the chunk's reverse composite (a's steps, then b's), reverse scan over the cell's 32 lanes, and the value
+// each sub-chunk's B2 starts from: `b` the one behind the chunk, `a` b's composite applied to it
+__device__ __forceinline__ void gsub_rscan(double Pa, double Ga, double Ha, double Pb, double Gb, double Hb, int lane,
+                                           double &XnA, double &VnA, double &XnB, double &VnB) {
+    constexpr int LPC = 32;
+    double G = fma(Pa, Gb, Ga), H = fma(Pa * Pa, Hb, Ha), Pi = Pa * Pb;
+#define RSCAN_ROUND(n)                                                     \
+    {                                                                  \
+        const double Pq = dpp1<DPP_ROW_SHL(n)>(Pi);                    \
+        const double Gq = dppz<DPP_ROW_SHL(n)>(G);                     \
+        const double Hq = dppz<DPP_ROW_SHL(n)>(H);                     \
+        G = fma(Pi, Gq, G);                                            \
+        H = fma(Pi * Pi, Hq, H);                                       \
+        Pi *= Pq;                                                      \
+    }
+    RSCAN_ROUND(1) RSCAN_ROUND(2) RSCAN_ROUND(4) RSCAN_ROUND(8)
+#undef RSCAN_ROUND
+    rscan_cross<LPC>(Pi, G, H, lane);
+    XnB = dppd<DPP_WAVE_SHL1, 0xF>(0.0, G);
+    VnB = dppd<DPP_WAVE_SHL1, 0xF>(0.0, H);
+    if ((lane & (LPC - 1)) == LPC - 1) { XnB = 0.0; VnB = 0.0; }
+    XnA = fma(Pb, XnB, Gb);
+    VnA = fma(Pb * Pb, VnB, Hb);
+}
+
+// B2 of a sub-chunk from (Xn, Vn) behind it: the recurrence, then the M-step sums from zero
+template <int PP, int QQ, int L, int HR>
+__device__ __forceinline__ void gsub_b2(const GsubLane &sb, bool act, double Xn, double Vn, double (&gv)[gsub_la(L)],
+                                        const double (&Jv)[gsub_la(L)], double hreg, GsubOut<PP, QQ> &o) {
+    constexpr int LPC = 32, KV = img_values(PP, QQ), KH2 = 2 * (KV / 2), LA = gsub_la(L), LB = gsub_lb(L);
+    auto val = [&](int i, int v) -> double {
+        return (v < KH2 ? sb.yp : sb.yo[i & 1])[img_off(i, v, KV, LPC, L)];
+    };
+    double aSyx = 0.0, aTx1x = 0.0, aPall = 0.0;
+    double aSxv[QQ], aTx1u[PP], aTux[PP];
+#pragma unroll
+    for (int q_ = 0; q_ < QQ; q_++) aSxv[q_] = 0.0;
+#pragma unroll
+    for (int p_ = 0; p_ < PP; p_++) { aTx1u[p_] = 0.0; aTux[p_] = 0.0; }
+    const double XnE = Xn;
+    auto b2a = [&](int i) {
+        const double h = (i == HR) ? hreg : sb.hp[i * 64];
+        const double J = Jv[i];
+        aTx1x = fma(Vn, J, aTx1x);                  // Vs_{t+1} J_t   (:180; J = 0 at t = T-1)
+        const double Xs = fma(J, Xn, gv[i]);        // :101
+        const double Vs = fma(J * J, Vn, h);        // :102
+        aPall += Vs;                                // :181,:183
+        gv[i] = Xs;
+        Xn = Xs;
+        Vn = Vs;
+    };
+    auto b2b = [&](int i) {
+        const double Xs = gv[i];
+        double Xnx = (i + 1 < LA) ? gv[i + 1 < LA ? i + 1 : i] : XnE;
+        if (i >= LB - 2) Xnx = (i == sb.ns - 1) ? XnE : Xnx;
+        aTx1x = fma(Xnx, Xs, aTx1x);                // :180
+#pragma unroll
+        for (int p_ = 0; p_ < PP; p_++) {
+            const double ut = val(i, 1 + p_);       // zero at t = T-1
+            aTx1u[p_] = fma(Xnx, ut, aTx1u[p_]);    // :190
+            aTux[p_] = fma(ut, Xs, aTux[p_]);       // :191
+        }
+        aPall = fma(Xs, Xs, aPall);
+        aSyx = fma(val(i, 0), Xs, aSyx);            // :151
+#pragma unroll
+        for (int q_ = 0; q_ < QQ; q_++) aSxv[q_] = fma(Xs, val(i, 1 + PP + q_), aSxv[q_]);   // :159
+        if ((i & 7) == 0) __builtin_amdgcn_sched_barrier(0);
+    };
+    if (act) {
+#pragma unroll
+        for (int i = LA - 1; i >= 0; i--)
+            if (i < LB - 1 || i < sb.ns) b2a(i);
+#pragma unroll
+        for (int i = LA - 1; i >= 0; i--)
+            if (i < LB - 1 || i < sb.ns) b2b(i);
+    }
+    o.X0v = Xn; o.V0v = Vn;        // Xs, Vs at the sub-chunk's first step
+    o.aSyx = aSyx; o.aTx1x = aTx1x; o.aPall = aPall;
+#pragma unroll
+    for (int q_ = 0; q_ < QQ; q_++) o.aSxv[q_] = aSxv[q_];
+#pragma unroll
+    for (int p_ = 0; p_ < PP; p_++) { o.aTx1u[p_] = aTx1u[p_]; o.aTux[p_] = aTux[p_]; }
+}
+
+// what the chunk leaves in its lane: sum(a) + sum(b)
+template <int PP, int QQ>
+__device__ __forceinline__ void gsub_combine(PairSweepOut<PP, QQ> &o, const GsubOut<PP, QQ> &a, const GsubOut<PP, QQ> &b) {
+    o.aSyx = a.aSyx + b.aSyx; o.aTx1x = a.aTx1x + b.aTx1x; o.aPall = a.aPall + b.aPall; o.aSxx = 0.0;
+    o.likq = a.likq + b.likq; o.lsp = a.lsp + b.lsp; o.sneg = a.sneg | b.sneg;
+    o.tLv = b.tLv; o.X0v = a.X0v; o.V0v = a.V0v;
+#pragma unroll
+    for (int q_ = 0; q_ < QQ; q_++) o.aSxv[q_] = a.aSxv[q_] + b.aSxv[q_];
+#pragma unroll
+    for (int p_ = 0; p_ < PP; p_++) { o.aTx1u[p_] = a.aTx1u[p_] + b.aTx1u[p_]; o.aTux[p_] = a.aTux[p_] + b.aTux[p_]; }
+}
+
+// v of the lanes of half 0 / of half 1, in every lane (one v_permlane32_swap per word)
+__device__ __forceinline__ void halves_w(unsigned v, unsigned &lo, unsigned &hi) {
+    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    lo = r[0]; hi = r[1];
+}
+__device__ __forceinline__ void halves_d(double v, double &lo, double &hi) {
+    unsigned ll, lh, hl, hh;
+    halves_w((unsigned)__double2loint(v), ll, hl);
+    halves_w((unsigned)__double2hiint(v), lh, hh);
+    lo = __hiloint2double((int)lh, (int)ll);
+    hi = __hiloint2double((int)hh, (int)hl);
+}
+
+// 32-lane driver: this lane's cell, sub-chunk a then b
+template <int PP, int QQ, int L, bool LIKOD>
+__device__ __forceinline__ void pair_gsub_sweeps32(PairSweepOut<PP, QQ> &o, const Theta<PP, QQ> &th, const double *ys, double *hs,
+                                                   int lane, int nl, int rp, bool need_lik) {
+    constexpr int LA = gsub_la(L), LB = gsub_lb(L);
+    const int vl = lane & 31;
+    const bool act = vl < nl, tail = vl < rp;
+    const GsubConst k = gsub_const<PP, QQ, L>(th);
+    const GsubLane sa = gsub_lane<PP, QQ, L>(ys, hs, vl, 0, 0, tail, vl == nl - 1);
+    const GsubLane sb = gsub_lane<PP, QQ, L>(ys, hs, vl, 1, LA, tail, vl == nl - 1);
+    double ga[LA], Ja[LA], gb[LA], Jb[LA];
+    const GsubRow ra = gsub_f1<PP, QQ, L>(k, th, sa, act, ga);
+    const GsubRow rb = gsub_f1<PP, QQ, L>(k, th, sb, act, gb);
+    const PMat Ma = gsub_f1_fin<L>(k, ra, sa.ns, act), Mb = gsub_f1_fin<L>(k, rb, sb.ns, act);
+    double Xa, Va, Xb, Vb;
+    gsub_entry(Ma, Mb, th.mu1, th.V1, vl, Xa, Va, Xb, Vb);
+    GsubOut<PP, QQ> oa, ob;
+    double Pa, Ga, Ha, Pb, Gb, Hb, hnone = 0.0, hlast = 0.0;
+    gsub_f2<PP, QQ, L, LIKOD, -1>(k, th, sa, act, need_lik, Xa, Va, ga, Ja, hnone, Pa, Ga, Ha, oa);
+    gsub_f2<PP, QQ, L, LIKOD, LB - 1>(k, th, sb, act, need_lik, Xb, Vb, gb, Jb, hlast, Pb, Gb, Hb, ob);
+    double XnA, VnA, XnB, VnB;
+    gsub_rscan(Pa, Ga, Ha, Pb, Gb, Hb, lane, XnA, VnA, XnB, VnB);
+    gsub_b2<PP, QQ, L, LB - 1>(sb, act, XnB, VnB, gb, Jb, hlast, ob);
+    gsub_b2<PP, QQ, L, -1>(sa, act, XnA, VnA, ga, Ja, hnone, oa);
+    gsub_combine(o, oa, ob);
+}
+
+// 64-lane driver: ONE cell (theta `th`, the same in both halves); half 0 does the `a` sub-chunks, half 1 the `b`
+template <int PP, int QQ, int L, bool LIKOD>
+__device__ __forceinline__ void pair_gsub_sweeps64(PairSweepOut<PP, QQ> &o, const Theta<PP, QQ> &th, const double *ys, double *hs,
+                                                   int lane, int nl, int rp, bool need_lik) {
+    constexpr int LA = gsub_la(L);
+    const int vl = lane & 31, sub = lane >> 5;
+    const bool act = vl < nl, tail = vl < rp;
+    const GsubConst k = gsub_const<PP, QQ, L>(th);
+    const GsubLane sm = gsub_lane<PP, QQ, L>(ys, hs, vl, sub, 0, tail, vl == nl - 1);
+    double gm[LA], Jm[LA];
+    const PMat Mm = gsub_f1_fin<L>(k, gsub_f1<PP, QQ, L>(k, th, sm, act, gm), sm.ns, act);
+    PMat Ma, Mb;
+    halves_d(Mm.m00, Ma.m00, Mb.m00); halves_d(Mm.m01, Ma.m01, Mb.m01); halves_d(Mm.m10, Ma.m10, Mb.m10);
+    halves_d(Mm.m11, Ma.m11, Mb.m11); halves_d(Mm.m20, Ma.m20, Mb.m20); halves_d(Mm.m21, Ma.m21, Mb.m21);
+    halves_d(Mm.m22, Ma.m22, Mb.m22);
+    double Xa, Va, Xb, Vb;
+    gsub_entry(Ma, Mb, th.mu1, th.V1, vl, Xa, Va, Xb, Vb);
+    GsubOut<PP, QQ> om;
+    double Pm, Gm, Hm, hnone = 0.0;
+    gsub_f2<PP, QQ, L, LIKOD, -1>(k, th, sm, act, need_lik, sub ? Xb : Xa, sub ? Vb : Va, gm, Jm, hnone, Pm, Gm, Hm, om);
+    double Pa, Ga, Ha, Pb, Gb, Hb;
+    halves_d(Pm, Pa, Pb); halves_d(Gm, Ga, Gb); halves_d(Hm, Ha, Hb);
+    double XnA, VnA, XnB, VnB;
+    gsub_rscan(Pa, Ga, Ha, Pb, Gb, Hb, lane, XnA, VnA, XnB, VnB);
+    gsub_b2<PP, QQ, L, -1>(sm, act, sub ? XnB : XnA, sub ? VnB : VnA, gm, Jm, hnone, om);
+    GsubOut<PP, QQ> oa, ob;
+    halves_d(om.aSyx, oa.aSyx, ob.aSyx); halves_d(om.aTx1x, oa.aTx1x, ob.aTx1x); halves_d(om.aPall, oa.aPall, ob.aPall);
+    halves_d(om.likq, oa.likq, ob.likq); halves_d(om.lsp, oa.lsp, ob.lsp);
+    halves_d(om.tLv, oa.tLv, ob.tLv); halves_d(om.X0v, oa.X0v, ob.X0v); halves_d(om.V0v, oa.V0v, ob.V0v);
+#pragma unroll
+    for (int q_ = 0; q_ < QQ; q_++) halves_d(om.aSxv[q_], oa.aSxv[q_], ob.aSxv[q_]);
+#pragma unroll
+    for (int p_ = 0; p_ < PP; p_++) { halves_d(om.aTx1u[p_], oa.aTx1u[p_], ob.aTx1u[p_]); halves_d(om.aTux[p_], oa.aTux[p_], ob.aTux[p_]); }
+    {
+        unsigned sl, sh;
+        halves_w((unsigned)om.sneg, sl, sh);
+        oa.sneg = (int)sl; ob.sneg = (int)sh;
+    }
+    gsub_combine(o, oa, ob);
+}
+
 // ---- G phase: generic iterations for the halves whose cell fails the verdict (`slow`, from the S loop's
 // verdict on entry: at least one iteration runs), until no cell of the wave fails.  A real function: the
 // generic sweeps keep 244 VGPRs busy, and entered once per slow episode the ~250 scratch accesses of
@@ -1363,7 +1849,37 @@ __device__ __attribute__((noinline)) PairCarry<PP, QQ> pair_steady_g_phase(PairE
         SCAN_TICK(7)
         const bool need_lik = pair_need_lik<PP, QQ, QUEUE>(E, cs, slow);
         PairSweepOut<PP, QQ> o;
-        pair_generic_sweeps<PP, QQ, L, LPC, true, !QUEUE>(o, cs.th, ys, hs, 0u, lane, nl, rp, cs.th.mu1, cs.th.V1, need_lik);
+        if constexpr (pair_gsub(PP, QQ)) {
+            // (what the epilogue derives from the cell's index and from n_obs -- result addresses, the likelihood's
+            // constants -- is loop invariant under the static schedule and was held in ~14 VGPRs through the sweeps,
+            // where the two sub-chunks' composites now live; opaque here, it is formed where it is used)
+            asm volatile("" : "+v"(cs.cell));
+            asm volatile("" : "+s"(E.n_obs));
+            // Width, wave-uniform: a lone slow cell runs on all 64 lanes, with its theta in both halves (the waiting
+            // half's own state stays in cs: the rest of the iteration passes it by, `slow` is false there); two slow
+            // cells run side by side as before.  Both drivers give a cell the same bits.
+            const unsigned long long sm = __ballot(slow);
+            const bool s0 = (unsigned)sm != 0u, s1 = (unsigned)(sm >> 32) != 0u;
+            if (LDSR_G_WIDTH != 32 && (LDSR_G_WIDTH == 64 || s0 != s1)) {
+                Theta<PP, QQ> tw;
+                auto pick = [&](double v) {
+                    double lo, hi;
+                    halves_d(v, lo, hi);
+                    return s1 ? hi : lo;
+                };
+                tw.A = pick(cs.th.A); tw.C = pick(cs.th.C); tw.Q = pick(cs.th.Q); tw.R = pick(cs.th.R);
+                tw.mu1 = pick(cs.th.mu1); tw.V1 = pick(cs.th.V1);
+#pragma unroll
+                for (int p_ = 0; p_ < PP; p_++) tw.B[p_] = pick(cs.th.B[p_]);
+#pragma unroll
+                for (int q_ = 0; q_ < QQ; q_++) tw.D[q_] = pick(cs.th.D[q_]);
+                pair_gsub_sweeps64<PP, QQ, L, !QUEUE>(o, tw, ys, hs, lane, nl, rp, need_lik);
+            } else {
+                pair_gsub_sweeps32<PP, QQ, L, !QUEUE>(o, cs.th, ys, hs, lane, nl, rp, need_lik);
+            }
+        } else {
+            pair_generic_sweeps<PP, QQ, L, LPC, true, !QUEUE>(o, cs.th, ys, hs, 0u, lane, nl, rp, cs.th.mu1, cs.th.V1, need_lik);
+        }
         SCAN_TICK(6)       // the generic sweeps
         pair_steady_finish<PP, QQ, QUEUE>(E, cs, o, 0.0, 0.0, slow, lane, c0, nc, nl - 1, need_lik);
         const PairVarBlk vb = pair_var_block<L>(cs.th.V1, cs.th.A, cs.th.C, cs.th.Q, cs.th.R, cs.alive, vl, hbase, shape_ok);
