@@ -45,6 +45,9 @@
  *                            LDS_rep(...) draw for draw
  *   ldsr_pcr_batch           the benchmark model R/PCR.R: every (member, fold) least-squares fit of cvPCR /
  *                            PCR_ensemble_selection (one_pcr_cv :101-107) and PCR_reconstruction's lm + predict
+ *   ldsr_filter_batch        replaces nothing the reference exports: it returns what Kalman_smoother computes on its
+ *                            way and discards (src/EM.cpp:43-90,115-120: Xp, Vp, Yp, Xu, Vu, delta, Sigma), the
+ *                            per-step likelihood terms and the statistics of the standardised innovations
  *
  * Data conventions (identical to the bytes R hands to .Call):
  *   y      [n_series][T]        double, NaN / NA_real_ = missing
@@ -368,6 +371,42 @@ int ldsr_bfgs_update_batch(int device, int n_series, int T, int p, int q, const 
  * kernel's parameter struct.  -> LDSR_OK, or LDSR_EINTERNAL with the field's name in ldsr_last_error(). */
 int ldsr_plg_extent_check(int kernel, int n_series, int T, int p, int q, int has_u, int has_v, int shared_uv,
                           const int *cell_offsets, int with_grad, long strip_short, long out_shift);
+
+/* The Kalman filter's own outputs and the innovation diagnostics: for every cell's theta
+ * the forward pass of Kalman_smoother (src/EM.cpp:43-90,115-120), kept instead of discarded.  Time is 0-based;
+ * obs_t = isfinite(y_t) (NaN, NA and +-Inf: missing); an absent u (v) drops the B u (D v) term.
+ *   Xp_0 = mu1, Vp_0 = V1;  t >= 1: Xp_t = A Xu_{t-1} + B u_{t-1}, Vp_t = A Vu_{t-1} A + Q
+ *   Yp_t = C Xp_t + D v_t;  S_t = C Vp_t C + R (every t);  e_t = y_t - Yp_t where obs_t, NaN elsewhere
+ *   obs_t: K = Vp_t C / S_t, Xu_t = Xp_t + K e_t, Vu_t = (1 - K C) Vp_t;  otherwise Xu_t = Xp_t, Vu_t = Vp_t
+ *   ll_t = -1/2 (log(2 pi) + log S_t + e_t^2 / S_t) where obs_t, 0 elsewhere
+ *   lik  = sum_t ll_t, divided by n_obs when stdlik: Kalman_smoother's lik (n_obs = 0: 0, NaN with stdlik)
+ *   z_t  = e_t / sqrt(S_t) at observed t;  zmean = their mean;  zvar = sum (z_t - zmean)^2 / n_obs
+ *   acf_k = sum over t with obs_t and obs_{t+k} of (z_t - zmean)(z_{t+k} - zmean) / sum over observed t of
+ *           (z_t - zmean)^2, k = 1 .. n_lags; NaN when no such pair exists or the denominator is 0 (this project's
+ *           own specification for series with holes)
+ * Outputs: the rows Xp, Vp, Yp, Xu, Vu, e, S, ll are [n_cells][T], each may be NULL (not written, not copied);
+ * lik [n_cells]; zstat [n_cells][2] = (zmean, zvar), may be NULL; acf [n_cells][n_lags], required exactly when
+ * n_lags > 0 (0 <= n_lags <= LDSR_FILTER_MAX_LAGS, n_lags < T); status [n_cells], may be NULL: LDSR_CELL_NONFINITE
+ * when sum_t ll_t is not finite (some S_t <= 0 at an observed step: the rows hold what the recursion produced), else
+ * LDSR_CELL_OK -- the sum before the division, so status does not depend on stdlik.  The filter does not whiten by
+ * Svv / Tuu: a series an EM call flags LDSR_CELL_SINGULAR is answered like any other.  One wavefront per cell, any T
+ * (filter.hip); a cell's numbers do not depend on the rows requested, on its place in the batch or on stdlik (lik
+ * apart), and are the same from both entries. */
+#define LDSR_FILTER_MAX_LAGS 32
+int ldsr_filter_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                      const double *v, int shared_uv, const int *cell_offsets, const double *theta, int stdlik,
+                      int n_lags, double *Xp, double *Vp, double *Yp, double *Xu, double *Vu, double *e, double *S,
+                      double *ll, double *lik, double *zstat, double *acf, int *status);
+/* The same with DEVICE pointers (cell_offsets stays a host array), asynchronous on `stream` (NULL = default stream):
+ * the call only enqueues.  d_workspace: at least ldsr_filter_workspace_bytes(...) bytes (0: unsupported arguments),
+ * 256-byte aligned; it holds the cell -> series map and, when n_lags > 0, the [n_cells][T] strip of z the lag pass
+ * reads.  A short workspace is refused before anything is written. */
+size_t ldsr_filter_workspace_bytes(int n_series, int T, int p, int q, int n_cells, int n_lags);
+int ldsr_filter_batch_device(int device, void *stream, int n_series, int T, int p, int q, const double *d_y,
+                             const double *d_u, const double *d_v, int shared_uv, const int *cell_offsets,
+                             const double *d_theta, int stdlik, int n_lags, double *d_Xp, double *d_Vp, double *d_Yp,
+                             double *d_Xu, double *d_Vu, double *d_e, double *d_S, double *d_ll, double *d_lik,
+                             double *d_zstat, double *d_acf, int *d_status, void *d_workspace, size_t workspace_bytes);
 
 /* Test hooks of the arenas' guard mode (LDSR_ARENA_GUARD=1 in the environment when the library is loaded; off, and
  * free, by default).  In that mode every buffer a host-pointer entry carves out of its arena is followed by a band of

@@ -13,56 +13,17 @@
 //   pass 4    forward: a_t (adjoint of Xs_t), coefficient J_{t-1}; the adjoint of J_t
 //   pass 5    backward: xp_t, then vp_t whose source needs xu_t of the same step; the parameter gradients
 // What a later pass needs of a step lies in the wave's strip of the device workspace (plgrad.h).  The per-step
-// arithmetic and every address are plgrad.h's host/device functions; this file adds the cross-lane part.
+// arithmetic and every address are plgrad.h's host/device functions, the cross-lane part is plgrad_lanes.h.
 //
 // Every product-sum is an explicit fma and contraction is off: the value is the same with and without the
 // gradient.
 #include "plgrad.h"
 #include "bfgs_impl.h"        // the optimiser; em_scan_impl.h: dppd, readlane_d, wave_sum_n
+#include "plgrad_lanes.h"     // aff_scan, mob_scan, lane_below, strip_sync
 
 #pragma clang fp contract(off)
 
 #define MAXPQ LDSR_MAXPQ
-
-template <int CTRL, int RM>
-__device__ __forceinline__ PlgAff aff_from(const PlgAff &x) {       // identity where the DPP source does not exist
-    return PlgAff{dppd<CTRL, RM>(1.0, x.a), dppd<CTRL, RM>(0.0, x.b)};
-}
-// inclusive scan over the lanes: lane l gets (map of lane l) after ... after (map of lane 0)
-__device__ __forceinline__ PlgAff aff_scan(PlgAff x) {
-    x = plg_aff_then(aff_from<DPP_ROW_SHR(1), 0xF>(x), x);
-    x = plg_aff_then(aff_from<DPP_ROW_SHR(2), 0xF>(x), x);
-    x = plg_aff_then(aff_from<DPP_ROW_SHR(4), 0xF>(x), x);
-    x = plg_aff_then(aff_from<DPP_ROW_SHR(8), 0xF>(x), x);
-    x = plg_aff_then(aff_from<DPP_ROW_BCAST15, 0xA>(x), x);          // lane 15 -> row 1, lane 47 -> row 3
-    x = plg_aff_then(aff_from<DPP_ROW_BCAST31, 0xC>(x), x);          // lane 31 -> rows 2, 3
-    return x;
-}
-
-template <int CTRL, int RM>
-__device__ __forceinline__ PlgMob mob_from(const PlgMob &x) {
-    return PlgMob{dppd<CTRL, RM>(1.0, x.m00), dppd<CTRL, RM>(0.0, x.m01), dppd<CTRL, RM>(0.0, x.m10),
-                  dppd<CTRL, RM>(1.0, x.m11)};
-}
-__device__ __forceinline__ PlgMob mob_scan(PlgMob x) {
-    x = plg_mob_then(mob_from<DPP_ROW_SHR(1), 0xF>(x), x);
-    x = plg_mob_then(mob_from<DPP_ROW_SHR(2), 0xF>(x), x);
-    x = plg_mob_then(mob_from<DPP_ROW_SHR(4), 0xF>(x), x);
-    x = plg_mob_then(mob_from<DPP_ROW_SHR(8), 0xF>(x), x);
-    x = plg_mob_then(mob_from<DPP_ROW_BCAST15, 0xA>(x), x);
-    x = plg_mob_then(mob_from<DPP_ROW_BCAST31, 0xC>(x), x);
-    return x;
-}
-
-// the value of the lane below (the step before in a forward pass, the step above in a backward one); lane 0
-// gets the carry of the chunk before
-__device__ __forceinline__ double lane_below(double carry, double x) { return dppd<DPP_WAVE_SHR1, 0xF>(carry, x); }
-
-// a wave's strip is written by one lane and read by another in the next pass
-__device__ __forceinline__ void strip_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // one wave's view of its cell
 struct PlgCell {
