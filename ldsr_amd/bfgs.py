@@ -19,9 +19,9 @@ CONVERGED, MAXIT, LINESEARCH, NONFINITE, INTERRUPTED = 0, 1, 2, 3, 4
 _START_STREAM = 1 << 40       # counter-mode stream of restart r: _START_STREAM + r
 
 
-def ssq_train(y, u, v, theta_packed, cell_offsets=None, grad=False, device=0):
-    """ssqTrain (R/LDS_GA.R:143-147) for a batch of packed thetas [n, 6+p+q]: the sum over the observed
-    y_t of (y_t - propagate(theta)$Y_t)^2.  With grad=True -> (ssq [n], gradient [n, 6+p+q])."""
+def _value_grad(entry, lam, y, u, v, theta_packed, cell_offsets, grad, device):
+    """ssq_train / pl_grad: marshal, call `entry` (lam: the argument only one of the two takes, else None) and
+    return the values, with grad=True (values, gradients)"""
     Y, U, V, S, T, p, q, shared = _series(y, u, v)
     theta = np.ascontiguousarray(np.atleast_2d(theta_packed), dtype=np.float64)
     if theta.shape[1] != 6 + p + q:
@@ -30,9 +30,15 @@ def ssq_train(y, u, v, theta_packed, cell_offsets=None, grad=False, device=0):
     off = _offsets(cell_offsets, S, n)
     f = np.empty(n)
     g = np.empty_like(theta) if grad else None
-    _lib.check(_lib.lib().ldsr_ssq_grad_batch(device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off),
-                                              _d(theta), _d(f), _d(g)))
+    _lib.check(getattr(_lib.lib(), entry)(device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off), _d(theta),
+                                          *([] if lam is None else [float(lam)]), _d(f), _d(g)))
     return (f, g) if grad else f
+
+
+def ssq_train(y, u, v, theta_packed, cell_offsets=None, grad=False, device=0):
+    """ssqTrain (R/LDS_GA.R:143-147) for a batch of packed thetas [n, 6+p+q]: the sum over the observed
+    y_t of (y_t - propagate(theta)$Y_t)^2.  With grad=True -> (ssq [n], gradient [n, 6+p+q])."""
+    return _value_grad("ldsr_ssq_grad_batch", None, y, u, v, theta_packed, cell_offsets, grad, device)
 
 
 def _bfgs_call(entry, lam, y, u, v, par0, lb, ub, cell_offsets, maxit, lmm, factr, pgtol, select, with_J, fit_mode,
@@ -88,17 +94,7 @@ def bfgs_batch(y, u, v, par0, lb, ub, cell_offsets=None, maxit=100, lmm=5, factr
 def pl_grad(y, u, v, theta_packed, lam, cell_offsets=None, grad=False, device=0):
     """penalized_likelihood (R/LDS_GA.R:28-44) for a batch of packed thetas [n, 6+p+q]: lik(stdlik=FALSE) -
     lam * ssq, one wavefront per theta.  With grad=True -> (pl [n], d pl / d theta [n, 6+p+q])."""
-    Y, U, V, S, T, p, q, shared = _series(y, u, v)
-    theta = np.ascontiguousarray(np.atleast_2d(theta_packed), dtype=np.float64)
-    if theta.shape[1] != 6 + p + q:
-        raise ValueError("theta must be [n, %d]" % (6 + p + q))
-    n = theta.shape[0]
-    off = _offsets(cell_offsets, S, n)
-    f = np.empty(n)
-    g = np.empty_like(theta) if grad else None
-    _lib.check(_lib.lib().ldsr_pl_grad_batch(device, S, T, p, q, _d(Y), _d(U), _d(V), shared, _i(off), _d(theta),
-                                             float(lam), _d(f), _d(g)))
-    return (f, g) if grad else f
+    return _value_grad("ldsr_pl_grad_batch", lam, y, u, v, theta_packed, cell_offsets, grad, device)
 
 
 def bfgs_update_batch(y, u, v, par0, lb, ub, lam=1.0, cell_offsets=None, maxit=100, lmm=5, factr=1e7, pgtol=0.0,
@@ -139,28 +135,33 @@ def start_points(lb, ub, num_restarts, seed=None, r_seed=None, first=0):
     return out
 
 
+def _learn(name, batch, y, u, v, ub, lb, num_restarts, seed, r_seed, kwargs):
+    """LDS_BFGS / LDS_BFGS_with_update: draw the start points, run `batch` (bfgs_batch / bfgs_update_batch, with
+    kwargs) on the one series and shape the reference's list; the fit has J where the batch gave one"""
+    if ub is None or lb is None:
+        raise ValueError("%s needs ub and lb" % name)     # R/LDS_reconstruction.R:176
+    p, q = _dims(u, v)
+    par0 = start_points(lb, ub, num_restarts, seed=seed, r_seed=r_seed)
+    r = batch(y, u, v, par0, lb, ub, **kwargs)
+    if r["theta"].shape[0] != 1:
+        raise ValueError("%s takes one series; %s runs several" % (name, batch.__name__))
+    k = int(r["winner"][0])
+    if k < 0:
+        raise _lib.LdsrError("%s: no restart has a finite objective value" % name)
+    fit = {key: r[key][0:1].copy() for key in ("X", "Y", "V", "J") if key in r}
+    fit["lik"] = float(r["lik"][0])
+    return {"theta": unpack_theta(r["theta"][0], p, q), "fit": fit, "lik": fit["lik"], "pl": float(r["value"][0]),
+            "all": dict(r["all"], selected=k, par0=par0)}
+
+
 def LDS_BFGS(y, u, v, ub=None, lb=None, num_restarts=100, seed=None, r_seed=None, select="reference",
              smooth=False, maxit=100, device=0):
     """-> {"theta", "fit", "lik", "pl", "all"}   (R/LDS_GA.R:176-183): theta as the reference's list, fit =
     propagate(theta, u, v, y) with the standardised likelihood (smooth=True: Kalman_smoother(y, u, v,
     theta), the BFGS_smooth arm, R/LDS_reconstruction.R:79-85), lik = fit's, pl = the selected restart's
     minimised ssq; "all" = the per-restart par / value / n_iter / n_eval / status (+ selected, par0)."""
-    if ub is None or lb is None:
-        raise ValueError("LDS_BFGS needs ub and lb")     # R/LDS_reconstruction.R:176
-    p, q = _dims(u, v)
-    par0 = start_points(lb, ub, num_restarts, seed=seed, r_seed=r_seed)
-    r = bfgs_batch(y, u, v, par0, lb, ub, maxit=maxit, select=select, smooth=smooth, device=device)
-    if r["theta"].shape[0] != 1:
-        raise ValueError("LDS_BFGS takes one series; bfgs_batch runs several")
-    k = int(r["winner"][0])
-    if k < 0:
-        raise _lib.LdsrError("LDS_BFGS: no restart has a finite objective value")
-    fit = {"X": r["X"][0:1].copy(), "Y": r["Y"][0:1].copy(), "V": r["V"][0:1].copy()}
-    if smooth:
-        fit["J"] = r["J"][0:1].copy()
-    fit["lik"] = float(r["lik"][0])
-    return {"theta": unpack_theta(r["theta"][0], p, q), "fit": fit, "lik": fit["lik"], "pl": float(r["value"][0]),
-            "all": dict(r["all"], selected=k, par0=par0)}
+    return _learn("LDS_BFGS", bfgs_batch, y, u, v, ub, lb, num_restarts, seed, r_seed,
+                  dict(maxit=maxit, select=select, smooth=smooth, device=device))
 
 
 def LDS_BFGS_with_update(y, u, v, lambda_=1.0, ub=None, lb=None, num_restarts=100, seed=None, r_seed=None,
@@ -169,17 +170,5 @@ def LDS_BFGS_with_update(y, u, v, lambda_=1.0, ub=None, lb=None, num_restarts=10
     Kalman_smoother(y, u, v, theta) with the standardised likelihood, lik = fit's, pl = the selected restart's
     minimised -penalized_likelihood; "all" = the per-restart par / value / n_iter / n_eval / status (+ selected,
     par0)."""
-    if ub is None or lb is None:
-        raise ValueError("LDS_BFGS_with_update needs ub and lb")
-    p, q = _dims(u, v)
-    par0 = start_points(lb, ub, num_restarts, seed=seed, r_seed=r_seed)
-    r = bfgs_update_batch(y, u, v, par0, lb, ub, lam=lambda_, maxit=maxit, select=select, device=device)
-    if r["theta"].shape[0] != 1:
-        raise ValueError("LDS_BFGS_with_update takes one series; bfgs_update_batch runs several")
-    k = int(r["winner"][0])
-    if k < 0:
-        raise _lib.LdsrError("LDS_BFGS_with_update: no restart has a finite objective value")
-    fit = {"X": r["X"][0:1].copy(), "Y": r["Y"][0:1].copy(), "V": r["V"][0:1].copy(), "J": r["J"][0:1].copy(),
-           "lik": float(r["lik"][0])}
-    return {"theta": unpack_theta(r["theta"][0], p, q), "fit": fit, "lik": fit["lik"], "pl": float(r["value"][0]),
-            "all": dict(r["all"], selected=k, par0=par0)}
+    return _learn("LDS_BFGS_with_update", bfgs_update_batch, y, u, v, ub, lb, num_restarts, seed, r_seed,
+                  dict(lam=lambda_, maxit=maxit, select=select, device=device))

@@ -16,36 +16,16 @@
 
 namespace ldsr_host {
 
-// ---- LDS_BFGS: ssqTrain, its gradient and the L-BFGS learner (bfgs.hip) ----------------------------
-// Both entries upload the raw series (the kernels read the ABI's time-major u, v as they are and find the
-// missing y_t themselves), the cell -> series map and the cells' thetas: a SeriesUpload with its cells.
-static SsqSeries ssq_series(const SeriesUpload &U, double *d_strip) {
-    SsqSeries S;
-    S.n_cells = U.cell_offsets[U.n_series]; S.T = U.T; S.p = U.p; S.q = U.q;
-    S.y = U.d_y; S.u = U.d_u; S.v = U.d_v;
-    S.u_stride = U.shared_uv ? 0 : (long)U.T * U.p; S.v_stride = U.shared_uv ? 0 : (long)U.T * U.q;
-    S.series_of_cell = U.d_soc; S.strip = d_strip;
-    return S;
-}
+// Every entry uploads the raw series (the kernels read the ABI's time-major u, v as they are and find the
+// missing y_t themselves), the cell -> series map and the cells' thetas: a SeriesUpload with its cells, whose
+// view() is the series side of the launch.  The strip of the workspace is the objective's own.
+// ssqTrain (LDS_BFGS, bfgs.hip): for the gradient, where T is beyond the LDS
 static size_t ssq_strip_bytes(int n_cells, int T) {
     return T <= BFGS_LDS_MAX_T ? 0 : sizeof(double) * 2 * (size_t)T * (size_t)bfgs_waves(n_cells, T);
 }
-
-// ---- LDS_BFGS_with_update: the penalised likelihood and its gradient (plgrad.hip) -----------------------
+// the penalised likelihood (LDS_BFGS_with_update, plgrad.hip): always
 static size_t plg_strip_bytes(int n_cells, int T) {
     return n_cells > 0 ? sizeof(double) * plg_launch_strip_doubles(n_cells, T) : 0;
-}
-// the series side of a launch from the block's offsets (what U.stage() hands out as d_y, d_u, d_v, d_soc)
-static PlgSeries plg_series(const SeriesUpload &U, char *dev, size_t o_strip) {
-    PlgSeries S;
-    S.n_cells = U.cell_offsets[U.n_series]; S.T = U.T; S.p = U.p; S.q = U.q;
-    S.y = (const double *)(dev + U.o_y);
-    S.u = U.u ? (const double *)(dev + U.o_u) : nullptr;
-    S.v = U.v ? (const double *)(dev + U.o_v) : nullptr;
-    S.u_stride = U.shared_uv ? 0 : (long)U.T * U.p; S.v_stride = U.shared_uv ? 0 : (long)U.T * U.q;
-    S.series_of_cell = (const int *)(dev + U.o_soc);
-    S.strip = (double *)(dev + o_strip);
-    return S;
 }
 // bytes the block reserves for y, u, v, series_of_cell and the strip (SeriesUpload::carve)
 struct PlgSeriesHave { size_t b[5]; };
@@ -64,17 +44,7 @@ static int refuse_bad_extent(const char *kernel, const PlgExtent *e, int n, cons
                 std::to_string(x.need) + " bytes of " + x.name + ", " + std::to_string(x.have) + " are reserved at offset " +
                 std::to_string((long long)((const char *)x.ptr - dev)) + " of a block of " + std::to_string(block_bytes));
 }
-static BfgsUpdateParams bfgs_update_params(const BfgsParams &bp, const PlgSeries &S, double lambda) {
-    BfgsUpdateParams up;
-    up.S = S;
-    up.par0 = bp.par0; up.lb = bp.lb; up.ub = bp.ub;
-    up.lambda = lambda;
-    up.maxit = bp.maxit; up.lmm = bp.lmm; up.ftol = bp.ftol; up.pgtol = bp.pgtol;
-    up.intr = bp.intr;
-    up.par = bp.par; up.value = bp.value; up.n_iter = bp.n_iter; up.n_eval = bp.n_eval; up.status = bp.status;
-    return up;
-}
-static int check_bfgs_update_extents(const BfgsUpdateParams &up, int n_series, const PlgSeriesHave &have, const char *dev,
+static int check_bfgs_update_extents(const BfgsParams &up, int n_series, const PlgSeriesHave &have, const char *dev,
                                      size_t block_bytes) {
     const int n_cells = up.S.n_cells, P = 6 + up.S.p + up.S.q;
     const size_t rows = sizeof(double) * (size_t)n_cells * P, vals = sizeof(double) * (size_t)n_cells;
@@ -90,47 +60,6 @@ static int check_bfgs_update_extents(const BfgsUpdateParams &up, int n_series, c
     e[n++] = PlgExtent{"n_eval", up.n_eval, sizeof(int) * plg_rows_doubles(n_cells, 1), ints, 1};
     e[n++] = PlgExtent{"status", up.status, sizeof(int) * plg_rows_doubles(n_cells, 1), ints, 1};
     return refuse_bad_extent("ldsr_bfgs_update_kernel", e, n, dev, block_bytes);
-}
-
-extern "C" int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q, const double *y,
-                                   const double *u, const double *v, int shared_uv, const int *cell_offsets,
-                                   const double *theta, double *ssq, double *grad) {
-    int rc = check_common(n_series, T, p, q, y, cell_offsets);
-    if (rc) return rc;
-    if (!theta || !ssq) return fail(LDSR_EINVAL, "theta and ssq must not be NULL");
-    const int n_cells = cell_offsets[n_series];
-    if (n_cells == 0) return LDSR_OK;
-    const int P = 6 + p + q;
-    ArenaLease lease;
-    rc = arena_acquire(device, &lease.a);
-    if (rc) return rc;
-    Arena *A = lease.a;
-    SeriesUpload U{n_series, T, p, q, y, u, v, shared_uv};
-    Carver c;
-    U.carve(c, cell_offsets, theta);
-    const size_t in_bytes = c.o;
-    const size_t o_f = c.take(sizeof(double) * (size_t)n_cells);
-    const size_t o_g = c.take(grad ? sizeof(double) * (size_t)n_cells * P : 0);
-    const size_t out_bytes = c.o - o_f;
-    const size_t strip_bytes = grad ? ssq_strip_bytes(n_cells, T) : 0;
-    const size_t o_strip = c.take(strip_bytes);
-    rc = arena_reserve(A, c, in_bytes + align256(out_bytes), "ldsr_ssq_grad_batch");
-    if (rc) return rc;
-    char *dev = A->dev, *pin = A->pin;
-    U.stage(A);
-    HIPCHK(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, A->stream));
-    SsqParams sp;
-    sp.S = ssq_series(U, strip_bytes ? (double *)(dev + o_strip) : nullptr);
-    sp.theta = U.d_theta;
-    sp.ssq = (double *)(dev + o_f);
-    sp.grad = grad ? (double *)(dev + o_g) : nullptr;
-    HIPCHK(launch_ssq_grad(sp, A->stream));
-    char *pout = pin + in_bytes;
-    HIPCHK(hipMemcpyAsync(pout, dev + o_f, out_bytes, hipMemcpyDeviceToHost, A->stream));
-    HIPCHK(hipStreamSynchronize(A->stream));
-    memcpy(ssq, pout, sizeof(double) * (size_t)n_cells);
-    if (grad) memcpy(grad, pout + (o_g - o_f), sizeof(double) * (size_t)n_cells * P);
-    return LDSR_OK;
 }
 
 // The block of ldsr_bfgs_batch / ldsr_bfgs_update_batch: [series | map | par0 | lb | ub | offsets] go up in one
@@ -178,11 +107,11 @@ struct BfgsCall {
         o_ws = c.take(L.total);
         total = c.o;
     }
-    // the pointers of the optimiser's launch (its scalars are the caller's); S: ssqTrain's series, after U.stage()
+    // the pointers of the optimiser's launch (its scalars are the caller's)
     BfgsParams params(char *dev) const {
         BfgsParams bp;
         memset(&bp, 0, sizeof(bp));
-        bp.S = ssq_series(U, !update && strip_bytes ? (double *)(dev + o_strip) : nullptr);
+        bp.S = U.view(dev, strip_bytes ? (double *)(dev + o_strip) : nullptr);
         bp.par0 = (const double *)(dev + U.o_th);
         bp.lb = (const double *)(dev + o_lb);
         bp.ub = (const double *)(dev + o_ub);
@@ -193,10 +122,7 @@ struct BfgsCall {
         bp.status = (int *)(dev + o_st);
         return bp;
     }
-    BfgsUpdateParams update_params(const BfgsParams &bp, char *dev, double lambda) const {
-        return bfgs_update_params(bp, plg_series(U, dev, o_strip), lambda);
-    }
-    int check(const BfgsUpdateParams &up, size_t strip_have, const char *dev) const {
+    int check(const BfgsParams &up, size_t strip_have, const char *dev) const {
         return check_bfgs_update_extents(up, U.n_series, plg_series_have(U, strip_have), dev, total);
     }
 };
@@ -244,20 +170,16 @@ static int run_bfgs(bool update, double lambda, int device, int n_series, int T,
     memcpy(pin + B.o_ub, ub, sizeof(double) * (size_t)P);
     memcpy(pin + B.o_off, cell_offsets, sizeof(int) * ((size_t)n_series + 1));
     BfgsParams bp = B.params(dev);
+    bp.lambda = lambda;
     bp.maxit = maxit; bp.lmm = lmm;
     bp.ftol = factr * 0x1p-52; bp.pgtol = pgtol;
     bp.intr = intr_flag_for_kernels();
-    const BfgsUpdateParams up = B.update_params(bp, dev, lambda);
     if (update && n_cells > 0) {        // (before anything is enqueued)
-        rc = B.check(up, B.strip_bytes, dev);
+        rc = B.check(bp, B.strip_bytes, dev);
         if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(dev, pin, B.in_bytes, hipMemcpyHostToDevice, A->stream));
-    if (!update) {
-        HIPCHK(launch_bfgs(bp, A->stream));
-    } else if (n_cells > 0) {
-        HIPCHK(launch_bfgs_update(up, A->stream));
-    }
+    HIPCHK(update ? launch_bfgs_update(bp, A->stream) : launch_bfgs(bp, A->stream));
     BfgsSelectParams sl;
     sl.n_series = n_series; sl.P = P; sl.select_max = select_max;
     sl.cell_offsets = (const int *)(dev + B.o_off);
@@ -356,13 +278,14 @@ extern "C" int ldsr_bfgs_update_batch(int device, int n_series, int T, int p, in
                     theta_w, value_w, lik_w, X, Y, V, J);
 }
 
-// The block of ldsr_pl_grad_batch: [series | map | theta] go up in one copy, [pl | grad] come back in one.
-struct PlGradCall {
+// The block of ldsr_ssq_grad_batch / ldsr_pl_grad_batch: [series | map | theta] go up in one copy, [value | grad]
+// come back in one; then the objective's strip (pl: the penalised likelihood, else ssqTrain).
+struct GradCall {
     SeriesUpload U;
     int n_cells, P;
     size_t in_bytes, o_f, o_g, g_bytes, out_bytes, o_strip, strip_bytes, total;
     Carver c;
-    PlGradCall(const SeriesUpload &series, const int *cell_offsets, const double *theta, bool grad) : U(series) {
+    GradCall(const SeriesUpload &series, const int *cell_offsets, const double *theta, bool pl, bool grad) : U(series) {
         n_cells = cell_offsets[U.n_series]; P = 6 + U.p + U.q;
         U.carve(c, cell_offsets, theta);
         in_bytes = c.o;
@@ -370,13 +293,14 @@ struct PlGradCall {
         g_bytes = grad ? sizeof(double) * (size_t)n_cells * P : 0;
         o_g = c.take(g_bytes);
         out_bytes = c.o - o_f;
-        strip_bytes = plg_strip_bytes(n_cells, U.T);
+        strip_bytes = pl ? plg_strip_bytes(n_cells, U.T) : grad ? ssq_strip_bytes(n_cells, U.T) : 0;
         o_strip = c.take(strip_bytes);
         total = c.o;
     }
+    // the launch's parameters: those of ldsr_pl_grad_kernel; ldsr_ssq_grad_kernel's are the same without lambda
     PlGradParams params(char *dev, double lambda) const {
         PlGradParams pp;
-        pp.S = plg_series(U, dev, o_strip);
+        pp.S = U.view(dev, strip_bytes ? (double *)(dev + o_strip) : nullptr);
         pp.theta = (const double *)(dev + U.o_th);
         pp.lambda = lambda;
         pp.pl = (double *)(dev + o_f);
@@ -393,34 +317,50 @@ struct PlGradCall {
     }
 };
 
-extern "C" int ldsr_pl_grad_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
-                                  const double *v, int shared_uv, const int *cell_offsets, const double *theta,
-                                  double lambda, double *pl, double *grad) {
+// One launch: the objective's value per cell and, where grad is asked for, its gradient.  pl: the penalised
+// likelihood at lambda, with the pre-launch extent check; else ssqTrain.
+static int run_value_grad(bool pl, double lambda, int device, int n_series, int T, int p, int q, const double *y,
+                          const double *u, const double *v, int shared_uv, const int *cell_offsets, const double *theta,
+                          double *value, double *grad) {
     int rc = check_common(n_series, T, p, q, y, cell_offsets);
     if (rc) return rc;
-    if (!theta || !pl) return fail(LDSR_EINVAL, "theta and pl must not be NULL");
+    if (!theta || !value) return fail(LDSR_EINVAL, pl ? "theta and pl must not be NULL" : "theta and ssq must not be NULL");
     if (!std::isfinite(lambda)) return fail(LDSR_EINVAL, "lambda must be finite");
     if (cell_offsets[n_series] == 0) return LDSR_OK;
     ArenaLease lease;
     rc = arena_acquire(device, &lease.a);
     if (rc) return rc;
     Arena *A = lease.a;
-    PlGradCall call(SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets, theta, grad != nullptr);
-    rc = arena_reserve(A, call.c, call.in_bytes + align256(call.out_bytes), "ldsr_pl_grad_batch");
+    GradCall call(SeriesUpload{n_series, T, p, q, y, u, v, shared_uv}, cell_offsets, theta, pl, grad != nullptr);
+    rc = arena_reserve(A, call.c, call.in_bytes + align256(call.out_bytes), pl ? "ldsr_pl_grad_batch" : "ldsr_ssq_grad_batch");
     if (rc) return rc;
     char *dev = A->dev, *pin = A->pin;
     call.U.stage(A);
     const PlGradParams pp = call.params(dev, lambda);
-    rc = call.check(pp, call.strip_bytes, dev);
-    if (rc) return rc;
+    if (pl) {
+        rc = call.check(pp, call.strip_bytes, dev);
+        if (rc) return rc;
+    }
     HIPCHK(hipMemcpyAsync(dev, pin, call.in_bytes, hipMemcpyHostToDevice, A->stream));
-    HIPCHK(launch_pl_grad(pp, A->stream));
+    HIPCHK(pl ? launch_pl_grad(pp, A->stream) : launch_ssq_grad(SsqParams{pp.S, pp.theta, pp.pl, pp.grad}, A->stream));
     char *pout = pin + call.in_bytes;
     HIPCHK(hipMemcpyAsync(pout, dev + call.o_f, call.out_bytes, hipMemcpyDeviceToHost, A->stream));
     HIPCHK(hipStreamSynchronize(A->stream));
-    memcpy(pl, pout, sizeof(double) * (size_t)call.n_cells);
+    memcpy(value, pout, sizeof(double) * (size_t)call.n_cells);
     if (grad) memcpy(grad, pout + (call.o_g - call.o_f), sizeof(double) * (size_t)call.n_cells * call.P);
     return LDSR_OK;
+}
+
+extern "C" int ldsr_ssq_grad_batch(int device, int n_series, int T, int p, int q, const double *y,
+                                   const double *u, const double *v, int shared_uv, const int *cell_offsets,
+                                   const double *theta, double *ssq, double *grad) {
+    return run_value_grad(false, 0.0, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta, ssq, grad);
+}
+
+extern "C" int ldsr_pl_grad_batch(int device, int n_series, int T, int p, int q, const double *y, const double *u,
+                                  const double *v, int shared_uv, const int *cell_offsets, const double *theta,
+                                  double lambda, double *pl, double *grad) {
+    return run_value_grad(true, lambda, device, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta, pl, grad);
 }
 
 extern "C" int ldsr_plg_extent_check(int kernel, int n_series, int T, int p, int q, int has_u, int has_v, int shared_uv,
@@ -430,8 +370,8 @@ extern "C" int ldsr_plg_extent_check(int kernel, int n_series, int T, int p, int
     if (rc) return rc;
     if (cell_offsets[n_series] < 1) return fail(LDSR_EINVAL, "the check needs at least one cell");
     char *const dev = (char *)(uintptr_t)0x100000;      // never dereferenced
-    PlGradCall call(SeriesUpload{n_series, T, p, q, &present, has_u ? &present : nullptr, has_v ? &present : nullptr,
-                                 shared_uv}, cell_offsets, nullptr, kernel == 1 || with_grad != 0);
+    GradCall call(SeriesUpload{n_series, T, p, q, &present, has_u ? &present : nullptr, has_v ? &present : nullptr,
+                               shared_uv}, cell_offsets, nullptr, true, kernel == 1 || with_grad != 0);
     const PlGradParams pp0 = call.params(dev, 1.0);
     const size_t strip_have = call.strip_bytes - (size_t)strip_short;
     if (kernel == 0) {
@@ -443,7 +383,7 @@ extern "C" int ldsr_plg_extent_check(int kernel, int n_series, int T, int p, int
     const BfgsCall B(call.U, cell_offsets, nullptr, true);
     BfgsParams bp = B.params(dev);
     bp.par = (double *)((char *)bp.par + out_shift);
-    return B.check(B.update_params(bp, dev, 1.0), B.strip_bytes - (size_t)strip_short, dev);
+    return B.check(bp, B.strip_bytes - (size_t)strip_short, dev);
 }
 
 }  // namespace ldsr_host

@@ -33,17 +33,6 @@ static int check_filter(int n_series, int T, int p, int q, const double *y, cons
     return LDSR_OK;
 }
 
-// the series side of a launch: device pointers as they are, u / v null: absent
-static PlgSeries filter_series(int n_cells, int n_series, int T, int p, int q, const double *d_y, const double *d_u,
-                               const double *d_v, int shared_uv, const int *d_soc) {
-    PlgSeries S;
-    S.n_cells = n_cells; S.T = T; S.p = p; S.q = q;
-    S.y = d_y; S.u = d_u; S.v = d_v;
-    S.u_stride = shared_uv ? 0 : (long)T * p; S.v_stride = shared_uv ? 0 : (long)T * q;
-    S.series_of_cell = d_soc; S.strip = nullptr;
-    return S;
-}
-
 extern "C" size_t ldsr_filter_workspace_bytes(int n_series, int T, int p, int q, int n_cells, int n_lags) {
     if (n_series < 1 || T < 2 || p < 1 || q < 1 || p > LDSR_MAXPQ || q > LDSR_MAXPQ || n_cells < 0) return 0;
     if (n_lags < 0 || n_lags > LDSR_FILTER_MAX_LAGS || n_lags >= T) return 0;
@@ -74,7 +63,7 @@ extern "C" int ldsr_filter_batch_device(int device, void *stream_, int n_series,
     rc = stage_h2d_async(device, stream, ws, soc.data(), sizeof(int) * (size_t)n_cells);
     if (rc) return rc;
     FilterParams fp;
-    fp.S = filter_series(n_cells, n_series, T, p, q, d_y, d_u, d_v, shared_uv, (const int *)ws);
+    fp.S = cell_series(n_cells, T, p, q, d_y, d_u, d_v, shared_uv, (const int *)ws, nullptr);
     fp.theta = d_theta; fp.stdlik = stdlik != 0; fp.n_lags = n_lags;
     set_rows(fp, FilterRows{{d_Xp, d_Vp, d_Yp, d_Xu, d_Vu, d_e, d_S, d_ll}});
     fp.lik = d_lik; fp.zstat = d_zstat; fp.acf = d_acf; fp.status = d_status;
@@ -114,7 +103,7 @@ extern "C" int ldsr_filter_batch(int device, int n_series, int T, int p, int q, 
     U.stage(A);
     HIPCHK(hipMemcpyAsync(dev, A->pin, in_bytes, hipMemcpyHostToDevice, A->stream));
     FilterParams fp;
-    fp.S = filter_series((int)n_cells, n_series, T, p, q, U.d_y, U.d_u, U.d_v, shared_uv, U.d_soc);
+    fp.S = U.view(dev, nullptr);
     fp.theta = U.d_theta; fp.stdlik = stdlik != 0; fp.n_lags = n_lags;
     FilterRows d;
     for (int i = 0; i < 8; i++) d.r[i] = host.r[i] ? (double *)(dev + o_row[i]) : nullptr;

@@ -1,38 +1,33 @@
 // bfgs.h -- launch interface of the L-BFGS learner (bfgs.hip): LDS_BFGS, R/LDS_GA.R:155-184, by the
-// specification in INTEGRATION.md ("The bound-constrained L-BFGS").  Included by bfgs.hip and
-// api_bfgs.hip only.
+// specification in INTEGRATION.md ("The bound-constrained L-BFGS").  Included by bfgs.hip, by plgrad.hip
+// (through bfgs_impl.h: the optimiser's parameter block is the same for both objectives) and by api_bfgs.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "plgrad.h"                   // CellSeries
 
 #define BFGS_MAX_LMM 8                // curvature pairs a wave can keep (lmm <= this)
 #define BFGS_LS_TRIALS 20             // line-search trials at most
 #define BFGS_LDS_MAX_T 4096           // 2 T doubles fit the 64 KiB of one workgroup up to here
 
-// The series side of a launch: cell c belongs to series series_of_cell[c].
-struct SsqSeries {
-    int n_cells, T, p, q;
-    const double *y;                  // [n_series][T], NaN / +-Inf = missing
-    const double *u, *v;              // time-major [.][T][p] / [.][T][q], or null
-    long u_stride, v_stride;          // doubles between two series (0: shared by all)
-    const int *series_of_cell;        // [n_cells]
-    double *strip;                    // [n_waves][2 T] where T > BFGS_LDS_MAX_T (else null: LDS)
-};
-
 struct SsqParams {
-    SsqSeries S;
+    CellSeries S;                     // S.strip: [n_waves][2 T] where T > BFGS_LDS_MAX_T (else null: LDS)
     const double *theta;              // [n_cells][P]
     double *ssq;                      // [n_cells]
     double *grad;                     // [n_cells][P] or null
 };
 
+// The optimiser's launch, on ssqTrain (launch_bfgs; S.strip as in SsqParams) or on -pl at lambda
+// (launch_bfgs_update, plgrad.h; S.strip as in PlGradParams).
 struct BfgsParams {
-    SsqSeries S;
+    CellSeries S;
     const double *par0;               // [n_cells][P]
     const double *lb, *ub;            // [P]
+    double lambda;                    // (ssqTrain ignores it)
     int maxit, lmm;
     double ftol, pgtol;               // ftol = factr * 2^-52
-    const int *intr;                  // host-pinned interrupt flag, or null
-    double *par, *value;              // [n_cells][P], [n_cells]
+    const int *intr;                  // host-pinned interrupt flag, or null (not part of the call's block)
+    double *par, *value;              // [n_cells][P], [n_cells]: the minimised ssq resp. -pl
     int *n_iter, *n_eval, *status;    // [n_cells]
 };
 

@@ -12,7 +12,7 @@
 // numbers of iterations, and a lone wave gives its LDS back the moment it is done.  In the vector
 // algebra lane i owns variable i (P = 6 + p + q <= 38); the coefficients the time passes need come out
 // of those lanes by v_readlane and stay in scalar registers.  In the forward pass lane l owns step
-// 64 k + l of chunk k, and x over a chunk is the inclusive affine scan of ldsr_simulate_kernel (DPP row
+// 64 k + l of chunk k, and x over a chunk is the inclusive scan AffineScan of plgrad_lanes.h (DPP row
 // shifts and broadcasts, one fma by a power of A per round).  The backward pass is the same scan run
 // from the other end: it walks the chunks downwards with the lanes mirrored (lane l owns step
 // 64 k + 63 - l), so lam_{t+1} is the lane below.  It needs x_t and r_t again: the forward pass leaves
@@ -22,66 +22,20 @@
 // Every product-sum is an explicit fma and contraction is off, so the forward pass gives the same f
 // with and without the gradient.
 #include "bfgs.h"
-#include "bfgs_impl.h"        // the optimiser; em_scan_impl.h: dppz / dppd, readlane_d, wave_sum_n
+#include "bfgs_impl.h"        // the optimiser; plgrad_lanes.h: cell_view, theta_lanes, AffineScan, wave_sum1
 
 #pragma clang fp contract(off)
 
 #define MAXPQ LDSR_MAXPQ
 
-// one wave's view of its cell
-struct SsqCell {
-    const double *y, *u, *v;      // the series' rows (u, v null: absent)
-    double *strip;                // [2 T]: x_t, then r_t
-    int T, p, q;
-};
-
-__device__ __forceinline__ SsqCell ssq_cell(const SsqSeries &S, int cell, double *lds_strip) {
-    const int s = S.series_of_cell[cell];
-    SsqCell c;
-    c.T = S.T; c.p = S.p; c.q = S.q;
-    c.y = S.y + (size_t)s * S.T;
-    c.u = S.u ? S.u + (size_t)s * S.u_stride : nullptr;
-    c.v = S.v ? S.v + (size_t)s * S.v_stride : nullptr;
-    c.strip = S.strip ? S.strip + (size_t)blockIdx.x * 2 * S.T : lds_strip;
-    return c;
-}
-
-// inclusive scan x_l = A x_{l-1} + e_l over the 64 lanes (ldsr_simulate_kernel's)
-struct AffineScan {
-    double A, A2, A4, A8, P16, P32;
-    __device__ __forceinline__ AffineScan(double A_, int lane) : A(A_) {
-        A2 = A * A; A4 = A2 * A2; A8 = A4 * A4;
-        const double A16 = A8 * A8;
-        P16 = A;
-        if (lane & 1) P16 *= A;
-        if (lane & 2) P16 *= A2;
-        if (lane & 4) P16 *= A4;
-        if (lane & 8) P16 *= A8;
-        P32 = (lane & 16) ? P16 * A16 : P16;
-    }
-    __device__ __forceinline__ double run(double x) const {
-        x = fma(A, dppz<DPP_ROW_SHR(1)>(x), x);
-        x = fma(A2, dppz<DPP_ROW_SHR(2)>(x), x);
-        x = fma(A4, dppz<DPP_ROW_SHR(4)>(x), x);
-        x = fma(A8, dppz<DPP_ROW_SHR(8)>(x), x);
-        x = fma(P16, dppd<DPP_ROW_BCAST15, 0xA>(0.0, x), x);    // lane 15 -> row 1, lane 47 -> row 3
-        x = fma(P32, dppd<DPP_ROW_BCAST31, 0xC>(0.0, x), x);    // lane 31 -> rows 2, 3
-        return x;
-    }
-};
-
 // f at the theta whose variable i sits in lane i (xv); with GRAD also the gradient, variable i in lane i
 // (0 in the lanes beyond P).  Both results are the same in every lane resp. wave-uniform.
+// strip: the wave's [2 T], x_t then r_t (GRAD only).
 template <bool GRAD>
-__device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane, double *g_out) {
+__device__ __forceinline__ double ssq_eval(const CellView &c, double *strip, double xv, int lane, double *g_out) {
     const int T = c.T, p = c.p, q = c.q;
-    const double A = readlane_d(xv, 0), C = readlane_d(xv, 1 + p), mu1 = readlane_d(xv, 4 + p + q);
-    double Bk[MAXPQ], Dk[MAXPQ];
-#pragma unroll
-    for (int k = 0; k < MAXPQ; k++) {
-        Bk[k] = (c.u && k < p) ? readlane_d(xv, 1 + k) : 0.0;
-        Dk[k] = (c.v && k < q) ? readlane_d(xv, 2 + p + k) : 0.0;
-    }
+    const ThetaLanes th = theta_lanes(c, xv);
+    const double A = th.co.A, C = th.co.C, mu1 = th.mu1;
     const AffineScan scan(A, lane);
 
     double red[2 + MAXPQ];          // f, sum r x, sum r v_k
@@ -102,7 +56,7 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
                 const double *ut = c.u + (size_t)(t - 1) * p;
 #pragma unroll
                 for (int k = 0; k < MAXPQ; k++)
-                    if (k < p) e = fma(Bk[k], ut[k], e);
+                    if (k < p) e = fma(th.Bk[k], ut[k], e);
             }
             if (c.v) {
                 const double *vr = c.v + (size_t)t * q;
@@ -110,7 +64,7 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
                 for (int k = 0; k < MAXPQ; k++)
                     if (k < q) {
                         vt[k] = vr[k];
-                        dv = fma(Dk[k], vt[k], dv);
+                        dv = fma(th.Dk[k], vt[k], dv);
                     }
             }
             yt = c.y[t];
@@ -123,8 +77,8 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
         red[0] = fma(r, r, red[0]);
         if (GRAD) {
             if (in) {
-                c.strip[t] = x;
-                c.strip[T + t] = r;
+                strip[t] = x;
+                strip[T + t] = r;
             }
             if (obs) {
                 red[1] = fma(r, x, red[1]);
@@ -134,11 +88,7 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
             }
         }
     }
-    if (!GRAD) {
-        double f1[1] = {red[0]};
-        wave_sum_n<1>(f1);
-        return f1[0];
-    }
+    if (!GRAD) return wave_sum1(red[0]);
     wave_sum_n<2 + MAXPQ>(red);
     const double f = red[0];
     double g = 0.0;
@@ -163,8 +113,8 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
         const bool in = t < T;
         double xt = 0.0, r = 0.0;
         if (in) {
-            xt = c.strip[t];
-            r = c.strip[T + t];
+            xt = strip[t];
+            r = strip[T + t];
         }
         double e = m2C * r;
         if (lane == 0) e = fma(A, carry, e);
@@ -196,25 +146,34 @@ __device__ __forceinline__ double ssq_eval(const SsqCell &c, double xv, int lane
     return f;
 }
 
+// the wave's strip: its [2 T] of the workspace, or of LDS where the launch has no workspace
+__device__ __forceinline__ double *ssq_strip(const CellSeries &S, double *lds_strip) {
+    return S.strip ? S.strip + (size_t)blockIdx.x * 2 * S.T : lds_strip;
+}
+
 __global__ __launch_bounds__(64) void ldsr_ssq_grad_kernel(SsqParams prm) {
     extern __shared__ double lds_strip[];
     const int lane = threadIdx.x;
     const int P = 6 + prm.S.p + prm.S.q;
+    double *const strip = ssq_strip(prm.S, lds_strip);
     for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
-        const SsqCell c = ssq_cell(prm.S, cell, lds_strip);
-        const double xv = lane < P ? prm.theta[(size_t)cell * P + lane] : 0.0;
+        const CellView c = cell_view(prm.S, cell);
+        const double xv = lane < P ? prm.theta[plg_row_at(cell, lane, P)] : 0.0;
         double f, g = 0.0;
-        if (prm.grad) f = ssq_eval<true>(c, xv, lane, &g);
-        else f = ssq_eval<false>(c, xv, lane, nullptr);
+        if (prm.grad) f = ssq_eval<true>(c, strip, xv, lane, &g);
+        else f = ssq_eval<false>(c, strip, xv, lane, nullptr);
         if (lane == 0) prm.ssq[cell] = f;
-        if (prm.grad && lane < P) prm.grad[(size_t)cell * P + lane] = g;
+        if (prm.grad && lane < P) prm.grad[plg_row_at(cell, lane, P)] = g;
     }
 }
 
 struct SsqObjective {
-    SsqCell c;
+    CellView c;
+    double *strip;
     template <bool GRAD>
-    __device__ __forceinline__ double eval(double x, int lane, double *g) const { return ssq_eval<GRAD>(c, x, lane, g); }
+    __device__ __forceinline__ double eval(double x, int lane, double *g) const {
+        return ssq_eval<GRAD>(c, strip, x, lane, g);
+    }
 };
 
 // The optimiser (bfgs_impl.h) on ssqTrain.
@@ -224,8 +183,9 @@ __global__ __launch_bounds__(64) void ldsr_bfgs_kernel(BfgsParams prm) {
     const int P = 6 + prm.S.p + prm.S.q;
     const bool mine = lane < P;
     const double lo = mine ? prm.lb[lane] : 0.0, hi = mine ? prm.ub[lane] : 0.0;
+    double *const strip = ssq_strip(prm.S, lds_strip);
     for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
-        const SsqObjective obj{ssq_cell(prm.S, cell, lds_strip)};
+        const SsqObjective obj{cell_view(prm.S, cell), strip};
         bfgs_cell(obj, prm, cell, P, lane, mine, lo, hi);
     }
 }

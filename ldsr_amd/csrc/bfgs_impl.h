@@ -7,16 +7,10 @@
 // the negative penalised likelihood (plgrad.hip: LDS_BFGS_with_update).
 #pragma once
 #include "bfgs.h"
-#include "em_scan_impl.h"     // wave_sum_n
+#include "plgrad_lanes.h"     // wave_sum1; em_scan_impl.h: wave_sum_n
 #include "../../include/ldsr_hip.h"
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ double wave_sum1(double x) {
-    double a[1] = {x};
-    wave_sum_n<1>(a);
-    return a[0];
-}
 
 __device__ __forceinline__ double wave_max1(double x) {      // x >= 0 or NaN; NaN in any lane gives NaN
     bool bad = x != x;
@@ -26,8 +20,8 @@ __device__ __forceinline__ double wave_max1(double x) {      // x >= 0 or NaN; N
 
 // One cell.  prm: the launch's parameters (par0, lb / ub as lo / hi of this lane, maxit, lmm, ftol, pgtol, intr
 // and the per-cell outputs par, value, n_iter, n_eval, status); mine: lane < P.
-template <class Obj, class Prm>
-__device__ __forceinline__ void bfgs_cell(const Obj &obj, const Prm &prm, int cell, int P, int lane, bool mine,
+template <class Obj>
+__device__ __forceinline__ void bfgs_cell(const Obj &obj, const BfgsParams &prm, int cell, int P, int lane, bool mine,
                                           double lo, double hi) {
     const double x_in = mine ? prm.par0[(size_t)cell * P + lane] : 0.0;
     double x = fmin(fmax(x_in, lo), hi);

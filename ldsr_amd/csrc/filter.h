@@ -25,7 +25,7 @@ PLG_HD size_t flt_z_bytes(int n_cells, int T, int n_lags) {
 PLG_HD size_t flt_ws_bytes(int n_cells, int T, int n_lags) { return flt_ws_soc_bytes(n_cells) + flt_z_bytes(n_cells, T, n_lags); }
 
 struct FilterParams {
-    PlgSeries S;                      // (S.strip is not used)
+    CellSeries S;                     // (S.strip is not used)
     const double *theta;              // [n_cells][P]
     int stdlik, n_lags;
     double *Xp, *Vp, *Yp, *Xu, *Vu, *e, *Sv, *ll;     // [n_cells][T] each, or null: not written

@@ -2,8 +2,8 @@
 // filtered state, the innovation and its variance, the per-step likelihood terms, and the mean, variance and
 // autocorrelations of the standardised innovations.
 //
-// One wave per (series, restart) cell; lane l of chunk ch owns step 64 ch + l, any T.  The pass is the forward
-// pass of plgrad.hip's pl_eval: Vp_t by the inclusive scan of the Riccati steps as 2 x 2 projective maps, then
+// One wave per (series, restart) cell; lane l of chunk ch owns step 64 ch + l, any T.  The pass is fwd_chunk of
+// plgrad_lanes.h, the one plgrad.hip's pl_eval runs forward: Vp_t by the inclusive scan of the Riccati steps as 2 x 2 projective maps, then
 // S_t, K_t, Vu_t of each lane's own step from its entry state with the reference's expressions; Xp_t by the
 // affine scan with A (1 - K_t C); a carry between chunks.  Every requested row goes straight from the owning
 // lane to memory (512 contiguous bytes per chunk).  lik is one wave sum at the end; zmean and zvar merge each
@@ -13,82 +13,36 @@
 // Every product-sum is an explicit fma and contraction is off: a cell's numbers do not depend on which rows
 // are requested, on where the cell sits in the batch or on stdlik (lik apart).
 #include "filter.h"
-#include "plgrad_lanes.h"     // aff_scan, mob_scan, lane_below, strip_sync; em_scan_impl.h: readlane_d, wave_sum_n
+#include "plgrad_lanes.h"     // cell_view, theta_lanes, fwd_chunk, wave_sum1, strip_sync
 #include "../../include/ldsr_hip.h"
 
 #pragma clang fp contract(off)
 
-#define MAXPQ LDSR_MAXPQ
-
-__device__ __forceinline__ double flt_wave_sum(double x) {
-    double a[1] = {x};
-    wave_sum_n<1>(a);
-    return a[0];
-}
-
 __global__ __launch_bounds__(64) void ldsr_filter_kernel(FilterParams prm) {
     const int lane = threadIdx.x;
-    const int T = prm.S.T, p = prm.S.p, q = prm.S.q, P = 6 + p + q;
+    const int T = prm.S.T, P = 6 + prm.S.p + prm.S.q;
     const int n_chunks = plg_chunks(T);
     for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
-        const int s = prm.S.series_of_cell[plg_row_at(cell, 0, 1)];
-        const double *const y = prm.S.y + plg_y_at(s, 0, T);
-        const double *const u = prm.S.u ? prm.S.u + plg_uv_at(s, prm.S.u_stride, 0, p, 0) : nullptr;
-        const double *const v = prm.S.v ? prm.S.v + plg_uv_at(s, prm.S.v_stride, 0, q, 0) : nullptr;
+        const CellView c = cell_view(prm.S, cell);
         const double xv = lane < P ? prm.theta[plg_row_at(cell, lane, P)] : 0.0;       // variable i of theta in lane i
-        const PlgCoef co = plg_coef(readlane_d(xv, 0), readlane_d(xv, 1 + p), readlane_d(xv, 2 + p + q),
-                                    readlane_d(xv, 3 + p + q));
-        const double mu1 = readlane_d(xv, 4 + p + q), V1 = readlane_d(xv, 5 + p + q);
-        double Bk[MAXPQ], Dk[MAXPQ];
-#pragma unroll
-        for (int k = 0; k < MAXPQ; k++) {
-            Bk[k] = (u && k < p) ? readlane_d(xv, 1 + k) : 0.0;
-            Dk[k] = (v && k < q) ? readlane_d(xv, 2 + p + k) : 0.0;
-        }
+        const ThetaLanes th = theta_lanes(c, xv);
         double *const zrow = prm.z ? prm.z + plg_row_at(cell, 0, T) : nullptr;
 
         // ---- the filter ----
         double ll_sum = 0.0;
         FltMoments mom = {0.0, 0.0, 0.0};
-        double carry_V = V1, carry_X = mu1;
+        double carry_V = th.V1, carry_X = th.mu1;
         for (int ch = 0; ch < n_chunks; ch++) {
-            const int t = plg_fwd_step(ch, lane);
-            const bool in = t < T;
-            double bu = 0.0, dv = 0.0, yt = NAN;
-            if (in) {
-                if (u) {
-#pragma unroll
-                    for (int k = 0; k < MAXPQ; k++)
-                        if (k < p) bu = fma(Bk[k], u[plg_uv_at(0, 0, t, p, k)], bu);
-                }
-                if (v) {
-#pragma unroll
-                    for (int k = 0; k < MAXPQ; k++)
-                        if (k < q) dv = fma(Dk[k], v[plg_uv_at(0, 0, t, q, k)], dv);
-                }
-                yt = y[plg_y_at(0, t, T)];
-            }
-            const bool obs = in && isfinite(yt);
-            const double ymdv = obs ? yt - dv : 0.0;
-            // the variance: Vp at the exit of every step, then each lane's own step from its entry state
-            const PlgMob m = mob_scan(in ? plg_mob_step(co, obs) : plg_mob_identity());
-            const double Vp_next = plg_mob_apply(m, carry_V);
-            const double Vp = lane_below(carry_V, Vp_next);
-            carry_V = readlane_d(Vp_next, 63);
-            double S, K, Vu;
-            plg_var_step(co, Vp, obs, &S, &K, &Vu);
-            // the mean
-            const PlgAff a = aff_scan(in ? plg_mean_step(co, K, ymdv, bu) : plg_aff_identity());
-            const double Xp_next = plg_aff_apply(a, carry_X);
-            const double Xp = lane_below(carry_X, Xp_next);
-            carry_X = readlane_d(Xp_next, 63);
-            const PlgFwd f = plg_fwd_step_values(co, Vp, Xp, obs, ymdv);
+            const FwdChunk fc = fwd_chunk(c, th, ch, lane, carry_V, carry_X);
+            const int t = fc.t;
+            const bool in = fc.in, obs = fc.obs;
+            const PlgFwd &f = fc.f;
             const double z = flt_z(f, obs);
             if (in) {
                 const size_t at = plg_row_at(cell, t, T);
-                if (prm.Xp) prm.Xp[at] = Xp;
-                if (prm.Vp) prm.Vp[at] = Vp;
-                if (prm.Yp) prm.Yp[at] = flt_yp(co, Xp, dv);
+                if (prm.Xp) prm.Xp[at] = fc.Xp;
+                if (prm.Vp) prm.Vp[at] = fc.Vp;
+                if (prm.Yp) prm.Yp[at] = flt_yp(th.co, fc.Xp, fc.dv);
                 if (prm.Xu) prm.Xu[at] = f.Xu;
                 if (prm.Vu) prm.Vu[at] = f.Vu;
                 if (prm.e) prm.e[at] = obs ? f.d : NAN;
@@ -99,12 +53,12 @@ __global__ __launch_bounds__(64) void ldsr_filter_kernel(FilterParams prm) {
             }
             // the chunk's moments of z, merged into the running ones (the same in every lane)
             const double cnt = (double)__popcll(__ballot(obs));
-            const double sum_c = flt_wave_sum(obs ? z : 0.0);
+            const double sum_c = wave_sum1(obs ? z : 0.0);
             const double mean_c = cnt > 0.0 ? sum_c / cnt : 0.0;
             const double dev = obs ? z - mean_c : 0.0;
-            mom = flt_moments_merge(mom, cnt, mean_c, flt_wave_sum(dev * dev));
+            mom = flt_moments_merge(mom, cnt, mean_c, wave_sum1(dev * dev));
         }
-        const double lik_sum = flt_wave_sum(ll_sum);
+        const double lik_sum = wave_sum1(ll_sum);
         if (lane == 0) {
             prm.lik[plg_row_at(cell, 0, 1)] = prm.stdlik ? lik_sum / mom.n : lik_sum;
             if (prm.status) prm.status[plg_row_at(cell, 0, 1)] = isfinite(lik_sum) ? LDSR_CELL_OK : LDSR_CELL_NONFINITE;
@@ -122,12 +76,12 @@ __global__ __launch_bounds__(64) void ldsr_filter_kernel(FilterParams prm) {
             bool any = false;
             for (int ch = 0; ch < n_chunks; ch++) {
                 const int t = plg_fwd_step(ch, lane);
-                if (t < T - k && isfinite(y[plg_y_at(0, t, T)]) && isfinite(y[plg_y_at(0, t + k, T)])) {
+                if (t < T - k && isfinite(c.y[plg_y_at(0, t, T)]) && isfinite(c.y[plg_y_at(0, t + k, T)])) {
                     num = fma(zrow[t] - mom.mean, zrow[t + k] - mom.mean, num);
                     any = true;
                 }
             }
-            const double tot = flt_wave_sum(num);
+            const double tot = wave_sum1(num);
             const bool pairs = __any(any);
             if (lane == 0) prm.acf[plg_row_at(cell, k - 1, prm.n_lags)] = (pairs && mom.M2 != 0.0) ? tot / mom.M2 : NAN;
         }

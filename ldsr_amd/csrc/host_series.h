@@ -1,11 +1,25 @@
 // host_series.h -- the series of a host-pointer call on their way to the device (api_fit.hip, api_ga.hip,
-// api_bfgs.hip), and api_fit.hip's smoother call for the learners' singular series.
+// api_bfgs.hip, api_filter.hip), the series side of a one-wave-per-cell launch, and api_fit.hip's smoother call for
+// the learners' singular series.
 #pragma once
 #include <cstring>
 
 #include "host_em.h"
+#include "plgrad.h"                   // CellSeries
 
 namespace ldsr_host {
+
+// The series side of a one-wave-per-cell launch (bfgs.hip, plgrad.hip, filter.hip) from device pointers as they
+// are: u / v null: absent; strip: the kernel's workspace or null.
+inline CellSeries cell_series(int n_cells, int T, int p, int q, const double *d_y, const double *d_u, const double *d_v,
+                              int shared_uv, const int *d_soc, double *d_strip) {
+    CellSeries S;
+    S.n_cells = n_cells; S.T = T; S.p = p; S.q = q;
+    S.y = d_y; S.u = d_u; S.v = d_v;
+    S.u_stride = shared_uv ? 0 : (long)T * p; S.v_stride = shared_uv ? 0 : (long)T * q;
+    S.series_of_cell = d_soc; S.strip = d_strip;
+    return S;
+}
 
 // ---- what the host-pointer entries of the smoother, GA and BFGS families share ----------------
 // The series of a call as they cross the ABI (u, v null: absent) and their part of its input block: carve() takes
@@ -43,6 +57,13 @@ struct SeriesUpload {
         for (int s = 0; s < n_series; s++)
             for (int cc = cell_offsets[s]; cc < cell_offsets[s + 1]; cc++) h_soc[cc] = s;
         if (theta) memcpy(A->pin + o_th, theta, sizeof(double) * (size_t)cell_offsets[n_series] * (6 + p + q));
+    }
+    // ... and of the carved series with their cells in the call's block at dev (what stage() hands out as d_y, d_u,
+    // d_v, d_soc; the offsets alone decide, so the extent check can ask before anything is staged)
+    CellSeries view(char *dev, double *d_strip) const {
+        return cell_series(cell_offsets[n_series], T, p, q, (const double *)(dev + o_y),
+                           u ? (const double *)(dev + o_u) : nullptr, v ? (const double *)(dev + o_v) : nullptr, shared_uv,
+                           (const int *)(dev + o_soc), d_strip);
     }
     // series_prep of the uploaded series into the workspace ws (layout *L)
     hipError_t prep(int device, hipStream_t stream, char *ws, const WsLayout *L) {

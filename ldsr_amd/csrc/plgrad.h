@@ -1,6 +1,8 @@
 // plgrad.h -- the penalised likelihood pl = lik - lambda ssq of LDS_BFGS_with_update (R/LDS_GA.R:90-127) and
 // its exact gradient: what plgrad.hip's kernels, its host code and the stand-alone host program of the tests
 // (tests/plgrad_host/main.cpp) share.  The quantities and recurrences are those of tests/plgrad_model.py.
+// Its series descriptor (CellSeries), the addresses of the series and of the per-cell rows and the extent check
+// serve every one-wave-per-cell kernel: bfgs.h, filter.h and host_series.h include this file for them.
 //
 // Everything a kernel computes per step and every address it forms is an inline host/device function of
 // this file, so the addressing can be walked and the arithmetic run on a CPU.  This file includes nothing
@@ -58,6 +60,17 @@ PLG_HD size_t plg_uv_at(int s, long stride, int t, int k, int j) {
 }
 PLG_HD size_t plg_row_at(int cell, int i, int P) { return (size_t)cell * (size_t)P + (size_t)i; }
 
+// The series side of a one-wave-per-cell launch (bfgs.hip, plgrad.hip, filter.hip): cell c belongs to series
+// series_of_cell[c].
+struct CellSeries {
+    int n_cells, T, p, q;
+    const double *y;                  // [n_series][T], NaN / +-Inf = missing
+    const double *u, *v;              // time-major [.][T][p] / [.][T][q], or null: absent
+    long u_stride, v_stride;          // doubles between two series (0: shared by all)
+    const int *series_of_cell;        // [n_cells]
+    double *strip;                    // the waves' workspace, as the kernel lays it out (null: it has none)
+};
+
 // doubles behind each pointer that a launch over n_series series / n_cells cells can touch: one past the
 // largest index the functions above give
 PLG_HD size_t plg_y_doubles(int n_series, int T) { return plg_y_at(n_series - 1, T - 1, T) + 1; }
@@ -70,33 +83,12 @@ PLG_HD size_t plg_launch_strip_doubles(int n_cells, int T) {
 }
 
 // ---- the parameter structs of the kernels -----------------------------------------------------------------
-struct PlgSeries {
-    int n_cells, T, p, q;
-    const double *y;                  // [n_series][T], NaN / +-Inf = missing
-    const double *u, *v;              // time-major [.][T][p] / [.][T][q], or null: absent
-    long u_stride, v_stride;
-    const int *series_of_cell;        // [n_cells]
-    double *strip;                    // [plg_waves(n_cells)][PLG_NSTRIP][T]
-};
-
 struct PlGradParams {
-    PlgSeries S;
+    CellSeries S;                     // S.strip: [plg_waves(n_cells)][PLG_NSTRIP][T]
     const double *theta;              // [n_cells][P]
     double lambda;
     double *pl;                       // [n_cells]
     double *grad;                     // [n_cells][P] or null
-};
-
-struct BfgsUpdateParams {
-    PlgSeries S;
-    const double *par0;               // [n_cells][P]
-    const double *lb, *ub;            // [P]
-    double lambda;
-    int maxit, lmm;
-    double ftol, pgtol;
-    const int *intr;                  // host-pinned interrupt flag, or null (not part of the call's block)
-    double *par, *value;              // [n_cells][P], [n_cells]: value = the minimised -pl
-    int *n_iter, *n_eval, *status;    // [n_cells]
 };
 
 // One device pointer of a launch: the bytes the kernel touches behind it (need), the bytes the host reserved
@@ -109,8 +101,8 @@ struct PlgExtent {
 };
 #define PLG_MAX_EXTENTS 16
 
-PLG_HD int plg_series_extents(const PlgSeries &S, int n_series, const size_t *have, PlgExtent *e) {
-    // have: bytes reserved for y, u, v, series_of_cell, strip
+PLG_HD int plg_series_extents(const CellSeries &S, int n_series, const size_t *have, PlgExtent *e) {
+    // have: bytes reserved for y, u, v, series_of_cell, strip (the strip of the pl kernels)
     int n = 0;
     e[n++] = PlgExtent{"y", S.y, sizeof(double) * plg_y_doubles(n_series, S.T), have[0], 1};
     e[n++] = PlgExtent{"u", S.u, sizeof(double) * plg_uv_doubles(n_series, S.u_stride, S.T, S.p), have[1], 0};
@@ -288,6 +280,7 @@ PLG_HD PlgContrib plg_contrib(const PlgCoef &c, const PlgBack &b, double xu, dou
 
 // ---- launch interface (plgrad.hip) ------------------------------------------------------------------------
 #if defined(__HIPCC__)
+struct BfgsParams;                    // (bfgs.h)
 hipError_t launch_pl_grad(const PlGradParams &prm, hipStream_t stream);
-hipError_t launch_bfgs_update(const BfgsUpdateParams &prm, hipStream_t stream);
+hipError_t launch_bfgs_update(const BfgsParams &prm, hipStream_t stream);
 #endif

@@ -18,96 +18,52 @@
 // Every product-sum is an explicit fma and contraction is off: the value is the same with and without the
 // gradient.
 #include "plgrad.h"
-#include "bfgs_impl.h"        // the optimiser; em_scan_impl.h: dppd, readlane_d, wave_sum_n
-#include "plgrad_lanes.h"     // aff_scan, mob_scan, lane_below, strip_sync
+#include "bfgs_impl.h"        // the optimiser
+#include "plgrad_lanes.h"     // cell_view, theta_lanes, fwd_chunk, aff_scan, lane_below, strip_sync
 
 #pragma clang fp contract(off)
 
 #define MAXPQ LDSR_MAXPQ
 
-// one wave's view of its cell
-struct PlgCell {
-    const double *y, *u, *v;      // the series' rows (u, v null: absent)
-    double *strip;                // the wave's [PLG_NSTRIP][T]
-    int T, p, q;
-    double lambda;
-};
-
-__device__ __forceinline__ PlgCell plg_cell(const PlgSeries &S, int cell, double lambda) {
-    const int s = S.series_of_cell[plg_row_at(cell, 0, 1)];
-    PlgCell c;
-    c.T = S.T; c.p = S.p; c.q = S.q; c.lambda = lambda;
-    c.y = S.y + plg_y_at(s, 0, S.T);
-    c.u = S.u ? S.u + plg_uv_at(s, S.u_stride, 0, S.p, 0) : nullptr;
-    c.v = S.v ? S.v + plg_uv_at(s, S.v_stride, 0, S.q, 0) : nullptr;
-    c.strip = S.strip + plg_wave_strip((int)blockIdx.x, S.T);
-    return c;
-}
-
 // pl at the theta whose variable i sits in lane i (xv); with GRAD also d pl / d theta, variable i in lane i
-// (0 in the lanes beyond P).  The value is the same in every lane.
+// (0 in the lanes beyond P).  The value is the same in every lane.  st: the wave's strip [PLG_NSTRIP][T].
 template <bool GRAD>
-__device__ __forceinline__ double pl_eval(const PlgCell &c, double xv, int lane, double *g_out) {
+__device__ __forceinline__ double pl_eval(const CellView &c, double *const st, double lambda, double xv, int lane,
+                                          double *g_out) {
     const int T = c.T, p = c.p, q = c.q;
+    // (theta_lanes of plgrad_lanes.h written out: through the helper the register allocator reloads more spilled
+    //  scalars in this unit, 41 v_readlane more, and ldsr_bfgs_update_kernel is 0.8 % slower at T = 813)
     const PlgCoef co = plg_coef(readlane_d(xv, 0), readlane_d(xv, 1 + p), readlane_d(xv, 2 + p + q),
                                 readlane_d(xv, 3 + p + q));
-    const double mu1 = readlane_d(xv, 4 + p + q), V1 = readlane_d(xv, 5 + p + q);
-    double *const st = c.strip;
+    ThetaLanes th;
+    th.co = co;
+    th.mu1 = readlane_d(xv, 4 + p + q);
+    th.V1 = readlane_d(xv, 5 + p + q);
+#pragma unroll
+    for (int k = 0; k < MAXPQ; k++) {
+        th.Bk[k] = (c.u && k < p) ? readlane_d(xv, 1 + k) : 0.0;
+        th.Dk[k] = (c.v && k < q) ? readlane_d(xv, 2 + p + k) : 0.0;
+    }
     const int n_chunks = plg_chunks(T);
 
     // ---- forward: the filter ----
     double lik_terms = 0.0;
     {
-        double Bk[MAXPQ], Dk[MAXPQ];
-#pragma unroll
-        for (int k = 0; k < MAXPQ; k++) {
-            Bk[k] = (c.u && k < p) ? readlane_d(xv, 1 + k) : 0.0;
-            Dk[k] = (c.v && k < q) ? readlane_d(xv, 2 + p + k) : 0.0;
-        }
-        double carry_V = V1, carry_X = mu1;
+        double carry_V = th.V1, carry_X = th.mu1;
         for (int ch = 0; ch < n_chunks; ch++) {
-            const int t = plg_fwd_step(ch, lane);
-            const bool in = t < T;
-            double bu = 0.0, dv = 0.0, yt = NAN;
-            if (in) {
-                if (c.u) {
-#pragma unroll
-                    for (int k = 0; k < MAXPQ; k++)
-                        if (k < p) bu = fma(Bk[k], c.u[plg_uv_at(0, 0, t, p, k)], bu);
-                }
-                if (c.v) {
-#pragma unroll
-                    for (int k = 0; k < MAXPQ; k++)
-                        if (k < q) dv = fma(Dk[k], c.v[plg_uv_at(0, 0, t, q, k)], dv);
-                }
-                yt = c.y[plg_y_at(0, t, T)];
-            }
-            const bool obs = in && isfinite(yt);
-            const double ymdv = obs ? yt - dv : 0.0;
-            // the variance: Vp at the exit of every step, then each lane's own step from its entry state
-            const PlgMob m = mob_scan(in ? plg_mob_step(co, obs) : plg_mob_identity());
-            const double Vp_next = plg_mob_apply(m, carry_V);
-            const double Vp = lane_below(carry_V, Vp_next);
-            carry_V = readlane_d(Vp_next, 63);
-            double S, K, Vu;
-            plg_var_step(co, Vp, obs, &S, &K, &Vu);
-            // the mean
-            const PlgAff a = aff_scan(in ? plg_mean_step(co, K, ymdv, bu) : plg_aff_identity());
-            const double Xp_next = plg_aff_apply(a, carry_X);
-            const double Xp = lane_below(carry_X, Xp_next);
-            carry_X = readlane_d(Xp_next, 63);
-            const PlgFwd f = plg_fwd_step_values(co, Vp, Xp, obs, ymdv);
-            if (in) {
-                lik_terms += f.lik_term;
-                const PlgAff sm = plg_smooth_step(co, f.Vu, f.Xu, Vp_next, Xp_next, t == T - 1);
+            const FwdChunk fc = fwd_chunk(c, th, ch, lane, carry_V, carry_X);
+            const int t = fc.t;
+            if (fc.in) {
+                lik_terms += fc.f.lik_term;
+                const PlgAff sm = plg_smooth_step(co, fc.f.Vu, fc.f.Xu, fc.Vp_next, fc.Xp_next, t == T - 1);
                 st[plg_strip_at(PLG_J, t, T)] = sm.a;
                 st[plg_strip_at(PLG_SRC, t, T)] = sm.b;
-                st[plg_strip_at(PLG_BU, t, T)] = bu;
+                st[plg_strip_at(PLG_BU, t, T)] = fc.bu;
                 if (GRAD) {
-                    st[plg_strip_at(PLG_VP, t, T)] = Vp;
-                    st[plg_strip_at(PLG_K, t, T)] = f.K;
-                    st[plg_strip_at(PLG_XP, t, T)] = Xp;
-                    st[plg_strip_at(PLG_D, t, T)] = f.d;
+                    st[plg_strip_at(PLG_VP, t, T)] = fc.Vp;
+                    st[plg_strip_at(PLG_K, t, T)] = fc.f.K;
+                    st[plg_strip_at(PLG_XP, t, T)] = fc.Xp;
+                    st[plg_strip_at(PLG_D, t, T)] = fc.f.d;
                 }
             }
         }
@@ -136,14 +92,14 @@ __device__ __forceinline__ double pl_eval(const PlgCell &c, double xv, int lane,
                 ssq = fma(e, e, ssq);
                 if (GRAD) {
                     st[plg_strip_at(PLG_XS, t, T)] = Xs;
-                    st[plg_strip_at(PLG_EB, t, T)] = -2.0 * c.lambda * e;
+                    st[plg_strip_at(PLG_EB, t, T)] = -2.0 * lambda * e;
                 }
             }
         }
     }
     double tot[2] = {lik_terms, ssq};
     wave_sum_n<2>(tot);
-    const double pl = plg_value(tot[0], tot[1], c.lambda);
+    const double pl = plg_value(tot[0], tot[1], lambda);
     strip_sync();           // (the next evaluation's forward pass overwrites what other lanes have just read)
     if (!GRAD) return pl;
 
@@ -248,12 +204,13 @@ __device__ __forceinline__ double pl_eval(const PlgCell &c, double xv, int lane,
 __global__ __launch_bounds__(64) void ldsr_pl_grad_kernel(PlGradParams prm) {
     const int lane = threadIdx.x;
     const int P = 6 + prm.S.p + prm.S.q;
+    double *const st = prm.S.strip + plg_wave_strip((int)blockIdx.x, prm.S.T);
     for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
-        const PlgCell c = plg_cell(prm.S, cell, prm.lambda);
+        const CellView c = cell_view(prm.S, cell);
         const double xv = lane < P ? prm.theta[plg_row_at(cell, lane, P)] : 0.0;
         double f, g = 0.0;
-        if (prm.grad) f = pl_eval<true>(c, xv, lane, &g);
-        else f = pl_eval<false>(c, xv, lane, nullptr);
+        if (prm.grad) f = pl_eval<true>(c, st, prm.lambda, xv, lane, &g);
+        else f = pl_eval<false>(c, st, prm.lambda, xv, lane, nullptr);
         if (lane == 0) prm.pl[plg_row_at(cell, 0, 1)] = f;
         if (prm.grad && lane < P) prm.grad[plg_row_at(cell, lane, P)] = g;
     }
@@ -261,24 +218,27 @@ __global__ __launch_bounds__(64) void ldsr_pl_grad_kernel(PlGradParams prm) {
 
 // f = -pl
 struct NegPlObjective {
-    PlgCell c;
+    CellView c;
+    double *strip;
+    double lambda;
     template <bool GRAD>
     __device__ __forceinline__ double eval(double x, int lane, double *g) const {
         double gp = 0.0;
-        const double f = -pl_eval<GRAD>(c, x, lane, GRAD ? &gp : nullptr);
+        const double f = -pl_eval<GRAD>(c, strip, lambda, x, lane, GRAD ? &gp : nullptr);
         if (GRAD) *g = -gp;
         return f;
     }
 };
 
 // The optimiser (bfgs_impl.h) on -pl.
-__global__ __launch_bounds__(64) void ldsr_bfgs_update_kernel(BfgsUpdateParams prm) {
+__global__ __launch_bounds__(64) void ldsr_bfgs_update_kernel(BfgsParams prm) {
     const int lane = threadIdx.x;
     const int P = 6 + prm.S.p + prm.S.q;
     const bool mine = lane < P;
     const double lo = mine ? prm.lb[lane] : 0.0, hi = mine ? prm.ub[lane] : 0.0;
+    double *const st = prm.S.strip + plg_wave_strip((int)blockIdx.x, prm.S.T);
     for (int cell = blockIdx.x; cell < prm.S.n_cells; cell += gridDim.x) {
-        const NegPlObjective obj{plg_cell(prm.S, cell, prm.lambda)};
+        const NegPlObjective obj{cell_view(prm.S, cell), st, prm.lambda};
         bfgs_cell(obj, prm, cell, P, lane, mine, lo, hi);
     }
 }
@@ -289,7 +249,7 @@ hipError_t launch_pl_grad(const PlGradParams &prm, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_bfgs_update(const BfgsUpdateParams &prm, hipStream_t stream) {
+hipError_t launch_bfgs_update(const BfgsParams &prm, hipStream_t stream) {
     if (prm.S.n_cells <= 0) return hipSuccess;
     hipLaunchKernelGGL(ldsr_bfgs_update_kernel, dim3((unsigned)plg_waves(prm.S.n_cells)), dim3(64), 0, stream, prm);
     return hipGetLastError();

@@ -20,10 +20,12 @@
 //
 // The scan multiplies by A^1 .. A^32: for |A| beyond ~1e9 these overflow where the serial
 // recursion would only have grown without bound; fitted models have |A| < 1.
-#include "em_scan_impl.h"     // dppz / dppd and the DPP control words
+#include "plgrad_lanes.h"     // AffineScan; em_scan_impl.h: readlane_d
 #include "ldsr_kernels.h"
 
 #include <stdint.h>
+
+#pragma clang fp contract(fast)       // (this unit's sums of products stay contracted: plgrad_lanes.h turns that off)
 
 // SplitMix64 finaliser of ldsr_amd/synth.py (_splitmix64): the increment, then the mix.
 __device__ __forceinline__ uint64_t sim_splitmix64(uint64_t x) {
@@ -111,15 +113,7 @@ __global__ __launch_bounds__(256, 4) void ldsr_simulate_kernel(SimParams prm) {
         U.key = sim_splitmix64(prm.seed ^ sim_splitmix64(stream));
     }
 
-    // powers of A for the scan: A^1, A^2, A^4, A^8 (row shifts), A^((l & 15) + 1) and A^((l & 31) + 1)
-    // (the row broadcasts)
-    const double A2 = A * A, A4 = A2 * A2, A8 = A4 * A4, A16 = A8 * A8;
-    double P16 = A;
-    if (lane & 1) P16 *= A;
-    if (lane & 2) P16 *= A2;
-    if (lane & 4) P16 *= A4;
-    if (lane & 8) P16 *= A8;
-    const double P32 = (lane & 16) ? P16 * A16 : P16;
+    const AffineScan scan(A, lane);
 
     const size_t out0 = ((size_t)m * prm.num_reps + rep) * (size_t)T;
     double carry = 0.0;
@@ -146,13 +140,7 @@ __global__ __launch_bounds__(256, 4) void ldsr_simulate_kernel(SimParams prm) {
         }
         if (lane == 0) e = fma(A, carry, e);
         // inclusive scan x_l = A x_{l-1} + e_l over the 64 lanes
-        double x = e;
-        x = fma(A, dppz<DPP_ROW_SHR(1)>(x), x);
-        x = fma(A2, dppz<DPP_ROW_SHR(2)>(x), x);
-        x = fma(A4, dppz<DPP_ROW_SHR(4)>(x), x);
-        x = fma(A8, dppz<DPP_ROW_SHR(8)>(x), x);
-        x = fma(P16, dppd<DPP_ROW_BCAST15, 0xA>(0.0, x), x);    // lane 15 -> row 1, lane 47 -> row 3
-        x = fma(P32, dppd<DPP_ROW_BCAST31, 0xC>(0.0, x), x);    // lane 31 -> rows 2, 3
+        const double x = scan.run(e);
         carry = readlane_d(x, 63);
         if (t < T) {
             const double y = C * x + w;

@@ -60,7 +60,7 @@ static void walk_addressing(int T) {
 
 static void check_extents() {
     char block[4096];
-    PlgSeries S;
+    CellSeries S;
     S.n_cells = 3; S.T = 4; S.p = 1; S.q = 2;
     S.y = (const double *)block; S.u = nullptr; S.v = (const double *)(block + 256);
     S.u_stride = 0; S.v_stride = 0;
