@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -158,6 +159,17 @@ PrepParams prep_params(int n_series, int T, int p, int q, int PP, int QQ, const 
     return pp;
 }
 
+// A launch's blocks {series, first cell, n cells} (blocks never straddle a series) as the kernels read them: the
+// table [series | first cell | n cells], each column n_blocks long
+typedef std::array<int, 3> Block;
+static std::vector<int> block_table(const std::vector<Block> &blocks) {
+    const size_t n = blocks.size();
+    std::vector<int> tab(3 * n);
+    for (size_t i = 0; i < n; i++)
+        for (size_t k = 0; k < 3; k++) tab[k * n + i] = blocks[i][k];
+    return tab;
+}
+
 int em_batch_device_impl(EmLaunch &E) {
     const int n_series = E.n_series, T = E.T, p = E.p, q = E.q;
     const int *cell_offsets = E.cell_offsets;
@@ -184,20 +196,16 @@ int em_batch_device_impl(EmLaunch &E) {
     HIPCHK(hipSetDevice(E.device));
     char *ws = (char *)E.workspace;
 
-    // block table: blocks never straddle a series.  Static schedule: (series, first cell, n cells of
-    // the block).  Work queue: (series, first cell of the SERIES, n cells of the series) -- waves pull
-    // cells from the per-series queue.
-    std::vector<int> tab, bc, bn;     // (tab: the series column, then the other two)
+    // block table.  Static schedule: (series, first cell, n cells of the block).  Work queue: (series, first
+    // cell of the SERIES, n cells of the series) -- waves pull cells from the per-series queue.
+    std::vector<Block> blocks;
     for (int s = 0; s < n_series; s++)
-        for (int c = cell_offsets[s]; c < cell_offsets[s + 1]; c += cpb) {
-            tab.push_back(s);
-            bc.push_back(pl.queue ? cell_offsets[s] : c);
-            bn.push_back(pl.queue ? cell_offsets[s + 1] - cell_offsets[s] : std::min(cpb, cell_offsets[s + 1] - c));
-        }
-    const int n_blocks = (int)tab.size();
+        for (int c = cell_offsets[s]; c < cell_offsets[s + 1]; c += cpb)
+            blocks.push_back(pl.queue ? Block{s, cell_offsets[s], cell_offsets[s + 1] - cell_offsets[s]}
+                                      : Block{s, c, std::min(cpb, cell_offsets[s + 1] - c)});
+    const int n_blocks = (int)blocks.size();
     if (n_blocks > L.max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow");
-    tab.insert(tab.end(), bc.begin(), bc.end());
-    tab.insert(tab.end(), bn.begin(), bn.end());
+    std::vector<int> tab = block_table(blocks);
     int *d_tab = (int *)(ws + L.blk);
     const bool scan_img = E.fit_follows || !pl.cpw;
     PrepParams pp = prep_params(n_series, T, p, q, PP, QQ, E.y, E.u, E.v, E.shared_uv, ws, L, scan_img);
@@ -311,7 +319,7 @@ int smoother_tables(const PreparedSeries &S, int n, const int *series_of_cell, i
     out->scan = smoother_is_scan(S.T, S.PP, S.QQ, *S.L, mode);
     if (!out->scan) return stage_h2d_async(S.device, S.stream, d_soc, series_of_cell, sizeof(int) * (size_t)n);
     const int cpb = em_scan_cells_per_block(S.T, S.PP, S.QQ);
-    std::vector<int> tab, bc, bn;           // (tab: the series column, then the other two)
+    std::vector<Block> blocks;
     for (int c = 0; c < n;) {
         if (skip_series && (*skip_series)[(size_t)series_of_cell[c]]) {      // (the caller runs these cells itself)
             c++;
@@ -319,16 +327,13 @@ int smoother_tables(const PreparedSeries &S, int n, const int *series_of_cell, i
         }
         int e = c + 1;
         while (e < n && e - c < cpb && series_of_cell[e] == series_of_cell[c]) e++;
-        tab.push_back(series_of_cell[c]);
-        bc.push_back(c);
-        bn.push_back(e - c);
+        blocks.push_back(Block{series_of_cell[c], c, e - c});
         c = e;
     }
-    out->n_blocks = (int)tab.size();
+    out->n_blocks = (int)blocks.size();
     if (out->n_blocks > S.L->max_blocks) return fail(LDSR_EINVAL, "internal: block table overflow (fit)");
     if (out->n_blocks == 0) return LDSR_OK;
-    tab.insert(tab.end(), bc.begin(), bc.end());
-    tab.insert(tab.end(), bn.begin(), bn.end());
+    const std::vector<int> tab = block_table(blocks);
     int *d_ws_tab = (int *)(S.ws + S.L->blk);
     out->d_tab = d_ws_tab;
     return stage_h2d_async(S.device, S.stream, d_ws_tab, tab.data(), sizeof(int) * tab.size());
@@ -382,7 +387,7 @@ int launch_smoother(const PreparedSeries &S, int n, const int *series_of_cell, c
                     const int *d_tab_prebuilt) {
     SmootherTables tb;
     if (d_tab_prebuilt && smoother_is_scan(S.T, S.PP, S.QQ, *S.L, mode)) {
-        tb.scan = true;
+        tb.scan = true;         // (the caller's own table of n blocks, not the workspace's: no max_blocks to check)
         tb.d_tab = d_tab_prebuilt;
         tb.n_blocks = n;
     } else {

@@ -1,5 +1,6 @@
 // api_grid.hip -- the host-pointer EM entries of the C ABI: slices of the cell grid over the devices, the restart
-// grid with its winners' fit, the group entry, and the restart selection rule.
+// grid with its winners' phase (one enqueue, one deliver, whoever selected), the group entry, and the restart
+// selection rule.
 #include <hip/hip_runtime.h>
 
 #include <unistd.h>
@@ -9,7 +10,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -18,57 +21,34 @@
 
 namespace ldsr_host {
 
-// ---- one contiguous slice of the cell grid on one device ---------------------------------------
-// Phase 1 (slice_run): ONE pinned->device copy of [y | u | v | theta0], series_prep + EM kernel,
-// ONE device->pinned copy of [theta | lik | n_iter | status].  Phase 2 (slice_fit_winners, the
-// restart-grid entry only): gather the winners' theta and likelihood traces on the device, one
-// smoother pass for them, one copy back.  The arena stays leased between the phases.
-struct Slice {
-    // inputs (host pointers already offset to the slice; `off` are local cell offsets)
-    int device = 0, n_series = 0, T = 0, p = 0, q = 0, shared_uv = 0, niter = 0, algo = 0;
-    int lead_steps = 0;      // data facts found in y (EmPlanIn): -1 fully observed, else the all-missing lead
-    EmPlan plan;             // what the batch launch ran
-    double tol = 0.0;
-    const double *y = nullptr, *u = nullptr, *v = nullptr, *theta0 = nullptr;
-    std::vector<int> off;
-    // Striped cut (make_slices): the slice holds EVERY series of the call and, of series s, the
-    // cells [g_lo[s], g_lo[s] + off[s+1] - off[s]) of the caller's arrays -- theta0 / theta / lik /
-    // n_iter / status / liks are the caller's whole arrays, gathered and scattered per series.
-    std::vector<int> g_lo;
-    const int *plan_off = nullptr;      // the whole call's offsets (EmLaunch), several devices only
-    int plan_ns = 0;
-    // host outputs of phase 1 (liks optional: the full [n_cells][niter] trace, NaN padded)
-    double *theta = nullptr, *lik = nullptr, *liks = nullptr;
-    int *n_iter = nullptr, *status = nullptr;
-    int max_winners = 0;        // > 0: reserve phase-2 buffers and keep the traces on the device
-    // Fused restart path (the whole grid on this one slice): selection, winner gather and the
-    // winners' fit are enqueued right behind the EM kernel and everything comes back with ONE
-    // synchronisation; the per-cell arrays cross PCIe only if the caller asked for them.
-    bool fuse = false, want_all = true;
-    int *h_winner = nullptr, *h_nit_w = nullptr;
-    double *h_theta_w = nullptr, *h_lik_w = nullptr, *h_liks_w = nullptr;
-    double *h_X = nullptr, *h_Y = nullptr, *h_V = nullptr, *h_J = nullptr;
-    bool fused_done = false;
-    // state
-    ArenaLease lease;
-    int n_cells = 0, PP = 0, QQ = 0, P = 0;
-    bool trace_on_device = false;
-    WsLayout L;
-    size_t wsb = 0;
-    size_t d_in = 0, d_y = 0, d_u = 0, d_v = 0, d_th0 = 0, d_off = 0, in_bytes = 0;      // device offsets
-    size_t d_out = 0, d_theta = 0, d_lik = 0, d_nit = 0, d_st = 0, out_bytes = 0;
-    size_t d_liks = 0, d_ws = 0;
-    size_t d_w = 0, w_bytes = 0;          // phase-2 device block
-    size_t p_in = 0, p_out = 0, p_w = 0;  // pinned offsets
+// The arguments of a host-pointer EM call, in the ABI's order; the entry fills it once and every slice refers to it.
+// theta .. liks are the caller's whole per-cell arrays (liks optional: the full [n_cells][niter] trace, NaN padded);
+// theta null (the restart grid on one slice only): nobody asked for them and they stay on the device.
+struct GridCall {
+    int n_series, T, p, q;
+    const double *y, *u, *v;
+    int shared_uv;
+    const int *cell_offsets;
+    const double *theta0;
+    int niter;
+    double tol;
+    int algo;
+    double *theta, *lik;
+    int *n_iter, *status;
+    double *liks;
+    int P() const { return 6 + p + q; }
 };
 
-static size_t liks_trace_cap_bytes() {
-    const char *e = getenv("LDSR_LIKS_TRACE_MAX_BYTES");
-    if (e && *e) return (size_t)strtoull(e, nullptr, 10);
-    return (size_t)8 << 30;
-}
+// the caller's winner outputs of the restart grid, one row per series (any of liks_w .. J may be NULL)
+struct WinnerOut {
+    int *winner;
+    double *theta_w, *lik_w;
+    int *n_iter_w;
+    double *liks_w, *X, *Y, *V, *J;
+    bool want_fit() const { return X || Y || V || J; }
+};
 
-// phase-2 block layout for n winners (offsets relative to its start)
+// the winners' block of a slice for n rows (offsets relative to its start)
 struct WinLayout {
     size_t cell, ser, theta, liks, X, Y, V, J, lik, st, theta0, blk, lik_w, nit_w, total;
     size_t out_begin, out_bytes;    // [cell | theta | liks | X | Y | V | J | lik | lik_w | nit_w] is copied back
@@ -96,64 +76,57 @@ static WinLayout win_layout(int n, int P, int T, int niter) {
     return W;
 }
 
-// the winners' fit of a slice: one pass at the n thetas of its phase-2 block dw, on the series phase 1 prepared in ws
-static int slice_fit(const Slice &S, char *ws, char *dw, const WinLayout &W, int n, const int *series_of_cell,
-                     const int *d_tab_prebuilt = nullptr) {
-    const PreparedSeries PS{S.device, S.lease.a->stream, S.T, S.p, S.q, S.PP, S.QQ, S.shared_uv, S.u != nullptr,
-                            S.v != nullptr, ws, &S.L};
-    const FitOut F{(double *)(dw + W.X), (double *)(dw + W.Y), (double *)(dw + W.V), (double *)(dw + W.J),
-                   (double *)(dw + W.lik), nullptr, (int *)(dw + W.st)};
-    return launch_smoother(PS, n, series_of_cell, (const double *)(dw + W.theta), 1, 0, 0.0, F, (int *)(dw + W.ser),
-                           d_tab_prebuilt);
+// ---- one slice of the cell grid on one device --------------------------------------------------
+// slice_enqueue: ONE pinned->device copy of [y | u | v | theta0 | offsets], series_prep + EM kernel.  The per-cell
+// block [theta | lik | n_iter | status] comes back in ONE device->pinned copy (slice_cells_enqueue, slice_scatter).
+// The restart grid's winners' phase works on the same arena, which stays leased as long as the slice lives.
+struct Slice {
+    const GridCall *call = nullptr;
+    int device = 0;
+    // Striped cut (make_slices): the slice holds EVERY series of the call and, of series s, the cells
+    // [g_lo[s], g_lo[s] + off[s+1] - off[s]) of the caller's arrays, gathered and scattered per series; `off` are
+    // its local cell offsets.  n_series: the call's, or 0 for a slice without cells.
+    int n_series = 0, n_cells = 0;
+    std::vector<int> off, g_lo;
+    const int *plan_off = nullptr;      // the whole call's offsets (EmLaunch), several devices only
+    int plan_ns = 0;
+    int max_winners = 0;        // > 0: reserve the winners' block and keep the traces on the device if they fit
+    // state
+    ArenaLease lease;
+    int lead_steps = 0;         // data facts found in y (EmPlanIn)
+    EmPlan plan;                // what the batch launch ran
+    bool trace_on_device = false;
+    WsLayout L;                 // (the winners' fit reuses the prepared series and the scan kernel's image)
+    WinLayout W;
+    size_t wsb = 0;
+    size_t d_in = 0, d_y = 0, d_u = 0, d_v = 0, d_th0 = 0, d_off = 0, in_bytes = 0;      // device offsets
+    size_t d_out = 0, d_theta = 0, d_lik = 0, d_nit = 0, d_st = 0, out_bytes = 0;
+    size_t d_liks = 0, d_ws = 0, d_w = 0;
+    size_t p_out = 0, p_w = 0;      // pinned offsets (the inputs are at 0)
+};
+
+static size_t liks_trace_cap_bytes() {
+    const char *e = getenv("LDSR_LIKS_TRACE_MAX_BYTES");
+    if (e && *e) return (size_t)strtoull(e, nullptr, 10);
+    return (size_t)8 << 30;
+}
+static bool trace_fits(int n_cells, int niter) {
+    return sizeof(double) * (size_t)n_cells * niter <= liks_trace_cap_bytes();
 }
 
-// per-cell results of the slice (pinned block `pout`) -> the caller's arrays, series by series
-static void slice_scatter(const Slice &S, const char *pout) {
-    const int P = S.P;
-    for (int s = 0; s < S.n_series; s++) {
-        const size_t lo = (size_t)S.off[(size_t)s], nc = (size_t)S.off[(size_t)s + 1] - lo, g = (size_t)S.g_lo[(size_t)s];
-        if (!nc) continue;
-        memcpy(S.theta + g * P, pout + (S.d_theta - S.d_out) + sizeof(double) * lo * P, sizeof(double) * nc * P);
-        memcpy(S.lik + g, pout + (S.d_lik - S.d_out) + sizeof(double) * lo, sizeof(double) * nc);
-        memcpy(S.n_iter + g, pout + (S.d_nit - S.d_out) + sizeof(int) * lo, sizeof(int) * nc);
-        memcpy(S.status + g, pout + (S.d_st - S.d_out) + sizeof(int) * lo, sizeof(int) * nc);
-    }
-}
-
-// the EM launch of a slice on its arena: the prepared inputs, the per-cell outputs and the workspace
-static EmLaunch slice_launch(const Slice &S) {
-    const Arena *A = S.lease.a;
-    EmLaunch E;
-    E.device = S.device; E.stream = A->stream;
-    E.n_series = S.n_series; E.T = S.T; E.p = S.p; E.q = S.q; E.shared_uv = S.shared_uv;
-    E.y = (const double *)(A->dev + S.d_y);
-    E.u = S.u ? (const double *)(A->dev + S.d_u) : nullptr;
-    E.v = S.v ? (const double *)(A->dev + S.d_v) : nullptr;
-    E.niter = S.niter; E.tol = S.tol;
-    E.theta = (double *)(A->dev + S.d_theta); E.lik = (double *)(A->dev + S.d_lik);
-    E.n_iter = (int *)(A->dev + S.d_nit); E.status = (int *)(A->dev + S.d_st);
-    E.workspace = A->dev + S.d_ws; E.workspace_bytes = S.wsb;
-    E.lead_steps = S.lead_steps;
-    return E;
-}
-
-static int slice_run(Slice &S) {
-    S.n_cells = S.off[S.n_series];
-    S.P = 6 + S.p + S.q;
-    S.PP = ldsr_pad_dim(S.p);
-    S.QQ = ldsr_pad_dim(S.q);
-    if (S.n_cells == 0) return LDSR_OK;
-    const int T = S.T, P = S.P, n = S.n_cells;
-    const size_t nuv = S.shared_uv ? 1 : (size_t)S.n_series;
+// the slice's block of its arena [inputs | per-cell outputs | trace | EM workspace | winners' block] and its
+// pinned mirror [inputs | per-cell outputs | winners' block] (same relative layouts as on the device)
+static int slice_layout(Slice &S) {
+    const GridCall &G = *S.call;
+    const int T = G.T, P = G.P(), n = S.n_cells;
+    const size_t nuv = G.shared_uv ? 1 : (size_t)S.n_series;
     int rc = arena_acquire(S.device, &S.lease.a);
     if (rc) return rc;
-    Arena *A = S.lease.a;
-
     Carver c;
     S.d_in = c.o;
     S.d_y = c.take(sizeof(double) * (size_t)S.n_series * T);
-    S.d_u = c.take(S.u ? sizeof(double) * nuv * T * S.p : 0);
-    S.d_v = c.take(S.v ? sizeof(double) * nuv * T * S.q : 0);
+    S.d_u = c.take(G.u ? sizeof(double) * nuv * T * G.p : 0);
+    S.d_v = c.take(G.v ? sizeof(double) * nuv * T * G.q : 0);
     S.d_th0 = c.take(sizeof(double) * (size_t)n * P);
     S.d_off = c.take(sizeof(int) * ((size_t)S.n_series + 1));
     S.in_bytes = c.o - S.d_in;
@@ -163,195 +136,261 @@ static int slice_run(Slice &S) {
     S.d_nit = c.take(sizeof(int) * (size_t)n);
     S.d_st = c.take(sizeof(int) * (size_t)n);
     S.out_bytes = c.o - S.d_out;
-    const size_t trace_bytes = sizeof(double) * (size_t)n * S.niter;
-    S.trace_on_device = S.liks != nullptr || (S.max_winners > 0 && trace_bytes <= liks_trace_cap_bytes());
-    S.d_liks = c.take(S.trace_on_device ? trace_bytes : 0);
-    S.wsb = ldsr_em_workspace_bytes(S.n_series, T, S.p, S.q, n, S.algo);
+    S.trace_on_device = G.liks != nullptr || (S.max_winners > 0 && trace_fits(n, G.niter));
+    S.d_liks = c.take(S.trace_on_device ? sizeof(double) * (size_t)n * G.niter : 0);
+    S.wsb = ldsr_em_workspace_bytes(S.n_series, T, G.p, G.q, n, G.algo);
     if (!S.wsb) return fail(LDSR_EINVAL, "unsupported (T, p, q, algo) combination");
     S.d_ws = c.take(S.wsb);
-    const WinLayout W = win_layout(std::max(S.max_winners, 1), P, T, S.niter);
-    S.d_w = c.take(S.max_winners > 0 ? W.total : 0);
-    S.w_bytes = S.max_winners > 0 ? W.total : 0;
-    // pinned: inputs, outputs, phase-2 block (same relative layouts as on the device)
-    S.p_in = 0;
+    S.W = win_layout(std::max(S.max_winners, 1), P, T, G.niter);
+    const size_t w_bytes = S.max_winners > 0 ? S.W.total : 0;
+    S.d_w = c.take(w_bytes);
     S.p_out = align256(S.in_bytes);
     S.p_w = S.p_out + align256(S.out_bytes);
-    const size_t pin_total = S.p_w + S.w_bytes;
-    rc = arena_reserve(A, c, pin_total, "the EM slice (ldsr_em_batch / _multi / ldsr_em_restart_grid / _groups)");
-    if (rc) return rc;
+    return arena_reserve(S.lease.a, c, S.p_w + w_bytes,
+                         "the EM slice (ldsr_em_batch / _multi / ldsr_em_restart_grid / _groups)");
+}
 
-    // stage inputs
-    char *pin = A->pin + S.p_in;
-    memcpy(pin + (S.d_y - S.d_in), S.y, sizeof(double) * (size_t)S.n_series * T);
-    {
-        bool all_obs = true;
-        const size_t ny = (size_t)S.n_series * T;
-        for (size_t i = 0; i < ny && all_obs; i++) all_obs = std::isfinite(S.y[i]);
-        // all-missing lead common to every series (the pair family's closed form)
-        int lead = T;
-        for (int s = 0; s < S.n_series && lead > 0; s++) {
-            int t = 0;
-            while (t < lead && !std::isfinite(S.y[(size_t)s * T + t])) t++;
-            lead = std::min(lead, t);
-        }
-        S.lead_steps = all_obs ? -1 : lead;
+// data facts of the series for the launch planner (EmPlanIn::lead_steps): -1 fully observed, else the all-missing
+// lead common to every series (the pair family's closed form)
+static int lead_steps(const double *y, int n_series, int T) {
+    if (std::all_of(y, y + (size_t)n_series * T, [](double x) { return std::isfinite(x); })) return -1;
+    int lead = T;
+    for (int s = 0; s < n_series && lead > 0; s++) {
+        int t = 0;
+        while (t < lead && !std::isfinite(y[(size_t)s * T + t])) t++;
+        lead = std::min(lead, t);
     }
-    if (S.u) memcpy(pin + (S.d_u - S.d_in), S.u, sizeof(double) * nuv * T * S.p);
-    if (S.v) memcpy(pin + (S.d_v - S.d_in), S.v, sizeof(double) * nuv * T * S.q);
+    return lead;
+}
+
+// the inputs into the pinned block (and what the planner wants to know of y), then the one upload
+static int slice_stage(Slice &S) {
+    const GridCall &G = *S.call;
+    const Arena *A = S.lease.a;
+    const int T = G.T, P = G.P();
+    const size_t nuv = G.shared_uv ? 1 : (size_t)S.n_series;
+    char *pin = A->pin;
+    memcpy(pin + (S.d_y - S.d_in), G.y, sizeof(double) * (size_t)S.n_series * T);
+    S.lead_steps = lead_steps(G.y, S.n_series, T);
+    if (G.u) memcpy(pin + (S.d_u - S.d_in), G.u, sizeof(double) * nuv * T * G.p);
+    if (G.v) memcpy(pin + (S.d_v - S.d_in), G.v, sizeof(double) * nuv * T * G.q);
     for (int s = 0; s < S.n_series; s++)      // this slice's cells of every series
         memcpy(pin + (S.d_th0 - S.d_in) + sizeof(double) * (size_t)S.off[(size_t)s] * P,
-               S.theta0 + (size_t)S.g_lo[(size_t)s] * P,
+               G.theta0 + (size_t)S.g_lo[(size_t)s] * P,
                sizeof(double) * (size_t)(S.off[(size_t)s + 1] - S.off[(size_t)s]) * P);
     memcpy(pin + (S.d_off - S.d_in), S.off.data(), sizeof(int) * ((size_t)S.n_series + 1));
     HIPCHK(hipMemcpyAsync(A->dev + S.d_in, pin, S.in_bytes, hipMemcpyHostToDevice, A->stream));
-
-    EmLaunch E = slice_launch(S);
-    E.cell_offsets = S.off.data();
-    E.theta0 = (const double *)(A->dev + S.d_th0);
-    E.algo = S.algo;
-    E.liks = S.trace_on_device ? (double *)(A->dev + S.d_liks) : nullptr;
-    E.liks_nanfill = S.liks != nullptr;
-    E.abort_flag = intr_flag_for_kernels();
-    E.plan_off = S.plan_off; E.plan_ns = S.plan_ns;
-    rc = em_batch_device_impl(E);
-    if (rc) return rc;
-    S.plan = E.plan;
-    S.L = E.layout;         // (phase 2 reuses the prepared series and the scan kernel's image)
-    char *pout = A->pin + S.p_out;
-    if (S.fuse && S.trace_on_device) {
-        // selection, winner extraction and the winners' fit behind the EM kernel, one sync
-        const int ns = S.n_series;
-        char *dw = A->dev + S.d_w, *pw = A->pin + S.p_w;
-        SelectParams sel;
-        sel.n_series = ns; sel.P = P; sel.c_index = 1 + S.p;
-        sel.off = (const int *)(A->dev + S.d_off);
-        sel.theta = (const double *)(A->dev + S.d_theta);
-        sel.lik = (const double *)(A->dev + S.d_lik);
-        sel.winner = (int *)(dw + W.cell);
-        HIPCHK(launch_select_winners(sel, A->stream));
-        GatherParams gp;
-        gp.n_w = ns; gp.P = P; gp.niter = S.niter;
-        gp.cell = (const int *)(dw + W.cell);
-        gp.theta = sel.theta;
-        gp.theta0 = (const double *)(A->dev + S.d_th0);
-        gp.n_iter = (const int *)(A->dev + S.d_nit);
-        gp.liks = (const double *)(A->dev + S.d_liks);
-        gp.theta_w = (double *)(dw + W.theta);
-        gp.theta0_w = (double *)(dw + W.theta0);
-        gp.liks_w = (double *)(dw + W.liks);
-        gp.lik = sel.lik;
-        gp.lik_w = (double *)(dw + W.lik_w);
-        gp.n_iter_w = (int *)(dw + W.nit_w);
-        gp.blk = (int *)(dw + W.blk);
-        HIPCHK(launch_gather_winners(gp, A->stream));
-        const bool want_fit = S.h_X || S.h_Y || S.h_V || S.h_J;
-        if (want_fit) {
-            std::vector<int> soc((size_t)ns);
-            for (int i = 0; i < ns; i++) soc[(size_t)i] = i;
-            char *ws = A->dev + S.d_ws;
-            rc = slice_fit(S, ws, dw, W, ns, soc.data(), (const int *)(dw + W.blk));
-            if (rc) return rc;
-        }
-        if (S.want_all)
-            HIPCHK(hipMemcpyAsync(pout, A->dev + S.d_out, S.out_bytes, hipMemcpyDeviceToHost, A->stream));
-        HIPCHK(hipMemcpyAsync(pw + W.out_begin, dw + W.out_begin, W.out_bytes, hipMemcpyDeviceToHost,
-                              A->stream));
-        HIPCHK(wait_stream(A->stream));
-        if (intr_raised()) return fail(LDSR_EINTERRUPTED, "interrupted by the caller's interrupt callback");
-        if (S.want_all) slice_scatter(S, pout);
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        memcpy(S.h_winner, pw + W.cell, sizeof(int) * ns);
-        memcpy(S.h_theta_w, pw + W.theta, sizeof(double) * (size_t)ns * P);
-        memcpy(S.h_lik_w, pw + W.lik_w, sizeof(double) * ns);
-        memcpy(S.h_nit_w, pw + W.nit_w, sizeof(int) * ns);
-        if (S.h_liks_w) memcpy(S.h_liks_w, pw + W.liks, sizeof(double) * (size_t)ns * S.niter);
-        double *rows[4] = {S.h_X, S.h_Y, S.h_V, S.h_J};
-        const size_t roff[4] = {W.X, W.Y, W.V, W.J};
-        for (int k = 0; k < 4; k++) {
-            if (!rows[k]) continue;
-            memcpy(rows[k], pw + roff[k], sizeof(double) * (size_t)ns * T);
-            for (int i = 0; i < ns; i++)      // series without a winner: the fit kernel skipped them
-                if (S.h_winner[i] < 0)
-                    for (int t = 0; t < T; t++) rows[k][(size_t)i * T + t] = nan;
-        }
-        S.fused_done = true;
-        return LDSR_OK;
-    }
-    HIPCHK(hipMemcpyAsync(pout, A->dev + S.d_out, S.out_bytes, hipMemcpyDeviceToHost, A->stream));
-    HIPCHK(wait_stream(A->stream));
-    slice_scatter(S, pout);
-    if (S.liks)     // the full trace goes straight to the caller's (pageable) array, series by series
-        for (int s = 0; s < S.n_series; s++) {
-            const size_t nc = (size_t)(S.off[(size_t)s + 1] - S.off[(size_t)s]);
-            if (nc)
-                HIPCHK(hipMemcpy(S.liks + (size_t)S.g_lo[(size_t)s] * S.niter,
-                                 A->dev + S.d_liks + sizeof(double) * (size_t)S.off[(size_t)s] * S.niter,
-                                 sizeof(double) * nc * S.niter, hipMemcpyDeviceToHost));
-        }
     return LDSR_OK;
 }
 
-// Phase 2.  w_series / w_cell: local series index and local cell index of each winner of this
-// slice; outputs are rows [i] of the given host arrays (any of liks_w .. J may be NULL).
-static int slice_fit_winners(Slice &S, int n_w, const int *w_series, const int *w_cell,
-                             double *liks_w, double *X, double *Y, double *V, double *J) {
-    if (n_w == 0) return LDSR_OK;
-    Arena *A = S.lease.a;
-    const int T = S.T, P = S.P, niter = S.niter;
-    HIPCHK(hipSetDevice(S.device));
-    const WinLayout W = win_layout(std::max(S.max_winners, 1), P, T, niter);
+// an EM launch of a slice on its arena: the uploaded series, the per-cell outputs and the workspace
+static EmLaunch slice_launch(const Slice &S) {
+    const GridCall &G = *S.call;
+    const Arena *A = S.lease.a;
+    EmLaunch E;
+    E.device = S.device; E.stream = A->stream;
+    E.n_series = S.n_series; E.T = G.T; E.p = G.p; E.q = G.q; E.shared_uv = G.shared_uv;
+    E.y = (const double *)(A->dev + S.d_y);
+    E.u = G.u ? (const double *)(A->dev + S.d_u) : nullptr;
+    E.v = G.v ? (const double *)(A->dev + S.d_v) : nullptr;
+    E.niter = G.niter; E.tol = G.tol;
+    E.theta = (double *)(A->dev + S.d_theta); E.lik = (double *)(A->dev + S.d_lik);
+    E.n_iter = (int *)(A->dev + S.d_nit); E.status = (int *)(A->dev + S.d_st);
+    E.workspace = A->dev + S.d_ws; E.workspace_bytes = S.wsb;
+    E.lead_steps = S.lead_steps;
+    return E;
+}
+
+// the batch launch: every cell of the slice from its theta0
+static int slice_em(Slice &S) {
+    const GridCall &G = *S.call;
+    const Arena *A = S.lease.a;
+    EmLaunch E = slice_launch(S);
+    E.cell_offsets = S.off.data();
+    E.theta0 = (const double *)(A->dev + S.d_th0);
+    E.algo = G.algo;
+    E.liks = S.trace_on_device ? (double *)(A->dev + S.d_liks) : nullptr;
+    E.liks_nanfill = G.liks != nullptr;
+    E.abort_flag = intr_flag_for_kernels();
+    E.plan_off = S.plan_off; E.plan_ns = S.plan_ns;
+    const int rc = em_batch_device_impl(E);
+    S.plan = E.plan;
+    S.L = E.layout;
+    return rc;
+}
+
+// everything up to the EM kernel, enqueued on the arena's stream; nothing waits
+static int slice_enqueue(Slice &S) {
+    int rc = slice_layout(S);
+    if (!rc) rc = slice_stage(S);
+    return rc ? rc : slice_em(S);
+}
+
+// per-cell results: the one copy to the pinned block, and from there (after the wait) to the caller's arrays,
+// series by series
+static hipError_t slice_cells_enqueue(const Slice &S) {
+    const Arena *A = S.lease.a;
+    return hipMemcpyAsync(A->pin + S.p_out, A->dev + S.d_out, S.out_bytes, hipMemcpyDeviceToHost, A->stream);
+}
+static void slice_scatter(const Slice &S) {
+    const GridCall &G = *S.call;
+    const char *pout = S.lease.a->pin + S.p_out;
+    const int P = G.P();
+    for (int s = 0; s < S.n_series; s++) {
+        const size_t lo = (size_t)S.off[(size_t)s], nc = (size_t)S.off[(size_t)s + 1] - lo, g = (size_t)S.g_lo[(size_t)s];
+        if (!nc) continue;
+        memcpy(G.theta + g * P, pout + (S.d_theta - S.d_out) + sizeof(double) * lo * P, sizeof(double) * nc * P);
+        memcpy(G.lik + g, pout + (S.d_lik - S.d_out) + sizeof(double) * lo, sizeof(double) * nc);
+        memcpy(G.n_iter + g, pout + (S.d_nit - S.d_out) + sizeof(int) * lo, sizeof(int) * nc);
+        memcpy(G.status + g, pout + (S.d_st - S.d_out) + sizeof(int) * lo, sizeof(int) * nc);
+    }
+}
+
+// a slice of the batch entries, and of a restart grid whose selection is the host's: run, wait, hand the cells back
+static int slice_run(Slice &S) {
+    if (S.n_cells == 0) return LDSR_OK;
+    const GridCall &G = *S.call;
+    const int rc = slice_enqueue(S);
+    if (rc) return rc;
+    const Arena *A = S.lease.a;
+    HIPCHK(slice_cells_enqueue(S));
+    HIPCHK(wait_stream(A->stream));
+    slice_scatter(S);
+    for (int s = 0; G.liks && s < S.n_series; s++) {    // the full trace goes straight to the caller's (pageable) array
+        const size_t lo = (size_t)S.off[(size_t)s], nc = (size_t)S.off[(size_t)s + 1] - lo;
+        if (nc)
+            HIPCHK(hipMemcpy(G.liks + (size_t)S.g_lo[(size_t)s] * G.niter, A->dev + S.d_liks + sizeof(double) * lo * G.niter,
+                             sizeof(double) * nc * G.niter, hipMemcpyDeviceToHost));
+    }
+    return LDSR_OK;
+}
+
+// ---- the winners' phase of the restart grid ----------------------------------------------------
+// winners_enqueue puts a slice's work for its winners on the stream behind the EM kernel and does not wait: the
+// gather of their theta, lik, n_iter and trace into the winners' block (the kernel also writes the fit's block table,
+// one winner per block), the re-run of the winners alone where the traces were too large to keep, the FIT smoother
+// when any of X / Y / V / J is wanted, and the copy of the block to pinned memory.  Row i of the block is the winner
+// of series rows[i] (ascending).  w_cell: its local cell index, uploaded with the series; null: the cells are in
+// W.cell already (select_winners_kernel: row i = series i, -1 = none).
+static int winners_enqueue(Slice &S, const std::vector<int> &rows, const int *w_cell, const WinnerOut &out) {
+    const GridCall &G = *S.call;
+    const Arena *A = S.lease.a;
+    const WinLayout &W = S.W;
+    const int n_w = (int)rows.size();
     char *dw = A->dev + S.d_w, *pw = A->pin + S.p_w;
-    memcpy(pw + W.cell, w_cell, sizeof(int) * n_w);
-    memcpy(pw + W.ser, w_series, sizeof(int) * n_w);
-    HIPCHK(hipMemcpyAsync(dw + W.cell, pw + W.cell, sizeof(int) * n_w, hipMemcpyHostToDevice, A->stream));
-    HIPCHK(hipMemcpyAsync(dw + W.ser, pw + W.ser, sizeof(int) * n_w, hipMemcpyHostToDevice, A->stream));
+    HIPCHK(hipSetDevice(S.device));
+    if (w_cell) {
+        memcpy(pw + W.cell, w_cell, sizeof(int) * n_w);
+        memcpy(pw + W.ser, rows.data(), sizeof(int) * n_w);
+        HIPCHK(hipMemcpyAsync(dw + W.cell, pw + W.cell, sizeof(int) * n_w, hipMemcpyHostToDevice, A->stream));
+        HIPCHK(hipMemcpyAsync(dw + W.ser, pw + W.ser, sizeof(int) * n_w, hipMemcpyHostToDevice, A->stream));
+    }
     GatherParams gp;
-    gp.n_w = n_w; gp.P = P; gp.niter = niter;
+    gp.n_w = n_w; gp.P = G.P(); gp.niter = G.niter;
     gp.cell = (const int *)(dw + W.cell);
-    gp.theta = (const double *)(A->dev + S.d_theta);
-    gp.theta0 = (const double *)(A->dev + S.d_th0);
-    gp.n_iter = (const int *)(A->dev + S.d_nit);
+    gp.ser = w_cell ? (const int *)(dw + W.ser) : nullptr;
+    gp.theta = (const double *)(A->dev + S.d_theta); gp.theta0 = (const double *)(A->dev + S.d_th0);
+    gp.lik = (const double *)(A->dev + S.d_lik); gp.n_iter = (const int *)(A->dev + S.d_nit);
     gp.liks = S.trace_on_device ? (const double *)(A->dev + S.d_liks) : nullptr;
-    gp.theta_w = (double *)(dw + W.theta);
-    gp.theta0_w = (double *)(dw + W.theta0);
+    gp.theta_w = (double *)(dw + W.theta); gp.theta0_w = (double *)(dw + W.theta0);
     gp.liks_w = (double *)(dw + W.liks);
-    gp.lik = nullptr; gp.lik_w = nullptr; gp.n_iter_w = nullptr; gp.blk = nullptr;
+    gp.lik_w = (double *)(dw + W.lik_w); gp.n_iter_w = (int *)(dw + W.nit_w);
+    gp.blk = (int *)(dw + W.blk);
     HIPCHK(launch_gather_winners(gp, A->stream));
-    char *ws = A->dev + S.d_ws;
-    if (!S.trace_on_device && liks_w) {
+    if (!S.trace_on_device && out.liks_w) {
         // the per-cell traces were too large to keep: re-run the winners alone (one cell per
         // series; a cell's result does not depend on its position in the grid) with a trace
         std::vector<int> sel_off((size_t)S.n_series + 1, 0);
-        for (int i = 0; i < n_w; i++) sel_off[(size_t)w_series[i] + 1] = 1;
+        for (int i = 0; i < n_w; i++) sel_off[(size_t)rows[(size_t)i] + 1] = 1;
         for (int s = 0; s < S.n_series; s++) sel_off[(size_t)s + 1] += sel_off[(size_t)s];
-        for (int i = 1; i < n_w; i++)
-            if (w_series[i] <= w_series[i - 1]) return fail(LDSR_EINVAL, "internal: winners must be sorted by series");
+        if (sel_off[(size_t)S.n_series] != n_w || !std::is_sorted(rows.begin(), rows.end()))
+            return fail(LDSR_EINVAL, "internal: winners must be sorted by series");
         EmLaunch E = slice_launch(S);
         E.cell_offsets = sel_off.data();
         E.theta0 = (const double *)(dw + W.theta0);
         E.algo = S.plan.algo;           // the kernel of the batch run, whatever AUTO would pick for a few cells
         E.lead_force = S.plan.lead;
         E.liks = (double *)(dw + W.liks);
-        int rc = em_batch_device_impl(E);
+        const int rc = em_batch_device_impl(E);
         if (rc) return rc;
     }
-    // the winners' fit: one smoother pass at theta_w on the prepared series
-    if (X || Y || V || J) {
-        std::vector<int> soc(w_series, w_series + n_w);
-        int rc = slice_fit(S, ws, dw, W, n_w, soc.data());
+    if (out.want_fit()) {       // one smoother pass at theta_w on the series the batch launch prepared
+        const PreparedSeries PS{S.device, A->stream, G.T, G.p, G.q, ldsr_pad_dim(G.p), ldsr_pad_dim(G.q), G.shared_uv,
+                                G.u != nullptr, G.v != nullptr, A->dev + S.d_ws, &S.L};
+        const FitOut F{(double *)(dw + W.X), (double *)(dw + W.Y), (double *)(dw + W.V), (double *)(dw + W.J),
+                       (double *)(dw + W.lik), nullptr, (int *)(dw + W.st)};
+        // (rows: the cell -> series map, uploaded to W.ser, of a shape only the serial smoother runs)
+        const int rc = launch_smoother(PS, n_w, rows.data(), (const double *)(dw + W.theta), 1, 0, 0.0, F,
+                                       (int *)(dw + W.ser), (const int *)(dw + W.blk));
         if (rc) return rc;
     }
-    HIPCHK(hipMemcpyAsync(pw + W.out_begin, dw + W.out_begin, W.out_bytes, hipMemcpyDeviceToHost,
-                          A->stream));
-    HIPCHK(hipStreamSynchronize(A->stream));
-    for (int i = 0; i < n_w; i++) {
-        if (liks_w) memcpy(liks_w + (size_t)i * niter, pw + W.liks + sizeof(double) * (size_t)i * niter, sizeof(double) * niter);
-        const size_t row = sizeof(double) * (size_t)i * T;
-        if (X) memcpy(X + (size_t)i * T, pw + W.X + row, sizeof(double) * T);
-        if (Y) memcpy(Y + (size_t)i * T, pw + W.Y + row, sizeof(double) * T);
-        if (V) memcpy(V + (size_t)i * T, pw + W.V + row, sizeof(double) * T);
-        if (J) memcpy(J + (size_t)i * T, pw + W.J + row, sizeof(double) * T);
+    HIPCHK(hipMemcpyAsync(pw + W.out_begin, dw + W.out_begin, W.out_bytes, hipMemcpyDeviceToHost, A->stream));
+    return LDSR_OK;
+}
+
+// a series without a winner (R's which.max on all-NA gives integer(0)): -1, NaN rows, no iterations
+static void fill_no_winner(const GridCall &G, const WinnerOut &out, int s) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    out.winner[s] = -1;
+    std::fill_n(out.theta_w + (size_t)s * G.P(), G.P(), nan);
+    out.lik_w[s] = nan;
+    out.n_iter_w[s] = 0;
+    if (out.liks_w) std::fill_n(out.liks_w + (size_t)s * G.niter, G.niter, nan);
+    for (double *r : {out.X, out.Y, out.V, out.J})
+        if (r) std::fill_n(r + (size_t)s * G.T, G.T, nan);
+}
+
+// After the wait: row i of the pinned winners' block -> row rows[i] of the caller's arrays, the winner as a cell
+// index of the whole call.  (Where the host selected, winner .. n_iter_w hold the same numbers already.)
+static void winners_deliver(const Slice &S, const std::vector<int> &rows, const WinnerOut &out) {
+    const GridCall &G = *S.call;
+    const WinLayout &W = S.W;
+    const char *pw = S.lease.a->pin + S.p_w;
+    const int *cell = (const int *)(pw + W.cell);
+    for (size_t i = 0; i < rows.size(); i++) {
+        const size_t s = (size_t)rows[i];
+        if (cell[i] < 0) {
+            fill_no_winner(G, out, (int)s);
+            continue;
+        }
+        auto row = [&](double *dst, size_t from, size_t len) {
+            if (dst) memcpy(dst + s * len, pw + from + sizeof(double) * i * len, sizeof(double) * len);
+        };
+        out.winner[s] = S.g_lo[s] + cell[i] - S.off[s];
+        out.lik_w[s] = ((const double *)(pw + W.lik_w))[i];
+        out.n_iter_w[s] = ((const int *)(pw + W.nit_w))[i];
+        row(out.theta_w, W.theta, (size_t)G.P());
+        row(out.liks_w, W.liks, (size_t)G.niter);
+        row(out.X, W.X, (size_t)G.T);
+        row(out.Y, W.Y, (size_t)G.T);
+        row(out.V, W.V, (size_t)G.T);
+        row(out.J, W.J, (size_t)G.T);
     }
+}
+
+// The whole restart grid on one slice, its traces on the device: selection and the winners' phase go on the stream
+// right behind the EM kernel and everything comes back with ONE wait; the per-cell arrays cross PCIe only if the
+// caller asked for them.
+static int slice_restart(Slice &S, const WinnerOut &out) {
+    const GridCall &G = *S.call;
+    int rc = slice_enqueue(S);
+    if (rc) return rc;
+    const Arena *A = S.lease.a;
+    SelectParams sel;
+    sel.n_series = S.n_series; sel.P = G.P(); sel.c_index = 1 + G.p;
+    sel.off = (const int *)(A->dev + S.d_off);
+    sel.theta = (const double *)(A->dev + S.d_theta); sel.lik = (const double *)(A->dev + S.d_lik);
+    sel.winner = (int *)(A->dev + S.d_w + S.W.cell);
+    HIPCHK(launch_select_winners(sel, A->stream));
+    std::vector<int> rows((size_t)S.n_series);
+    std::iota(rows.begin(), rows.end(), 0);
+    rc = winners_enqueue(S, rows, nullptr, out);
+    if (rc) return rc;
+    if (G.theta) HIPCHK(slice_cells_enqueue(S));
+    HIPCHK(wait_stream(A->stream));
+    if (intr_raised()) return fail(LDSR_EINTERRUPTED, "interrupted by the caller's interrupt callback");
+    if (G.theta) slice_scatter(S);
+    winners_deliver(S, rows, out);
     return LDSR_OK;
 }
 
@@ -363,20 +402,17 @@ static int slice_fit_winners(Slice &S, int n_w, const int *w_series, const int *
 // shares of every series are equal shares of the work (1.004 / 1.007 / 1.012 at 2 / 4 / 8 on the
 // same grid; tests/test_shard_gloo.py pins the bound).  Every slice carries all series (<= 100 KB
 // each) and the whole call's offsets for AUTO's plan.
-static void make_slices(std::vector<Slice> &sl, int n_devices, const int *devices, int n_series,
-                        int T, int p, int q, const double *y, const double *u, const double *v,
-                        int shared_uv, const int *cell_offsets, const double *theta0, int niter,
-                        double tol, int algo, double *theta, double *lik, int *n_iter,
-                        int *status, double *liks) {
+static void make_slices(std::vector<Slice> &sl, const GridCall &G, int n_devices, const int *devices) {
+    const int n_series = G.n_series;
     sl.resize((size_t)n_devices);
     for (int d = 0; d < n_devices; d++) {
         Slice &S = sl[(size_t)d];
+        S.call = &G;
         S.device = devices[d];
-        S.T = T; S.p = p; S.q = q; S.shared_uv = shared_uv; S.niter = niter; S.tol = tol; S.algo = algo;
         S.off.assign((size_t)n_series + 1, 0);
         S.g_lo.assign((size_t)n_series, 0);
         for (int s = 0; s < n_series; s++) {
-            const long long a = cell_offsets[s], ns = cell_offsets[s + 1] - cell_offsets[s];
+            const long long a = G.cell_offsets[s], ns = G.cell_offsets[s + 1] - G.cell_offsets[s];
             // part (d + s) mod n_devices of series s: the remainders of restart counts the device count
             // does not divide rotate over the devices (ldsr_amd/shard.py rank_slice is the same rule)
             const long long k = (d + s) % n_devices;
@@ -384,42 +420,54 @@ static void make_slices(std::vector<Slice> &sl, int n_devices, const int *device
             S.g_lo[(size_t)s] = lo;
             S.off[(size_t)s + 1] = S.off[(size_t)s] + (hi - lo);
         }
-        S.n_series = S.off[(size_t)n_series] > 0 ? n_series : 0;
-        S.y = y; S.u = u; S.v = v;
-        S.theta0 = theta0;
-        S.theta = theta; S.lik = lik; S.n_iter = n_iter; S.status = status; S.liks = liks;
-        if (n_devices > 1) { S.plan_off = cell_offsets; S.plan_ns = n_series; }
+        S.n_cells = S.off[(size_t)n_series];
+        S.n_series = S.n_cells > 0 ? n_series : 0;
+        if (n_devices > 1) { S.plan_off = G.cell_offsets; S.plan_ns = n_series; }
     }
 }
 
-// run phase 1 of every slice, one host thread per slice beyond the first
-static int run_slices(std::vector<Slice> &sl) {
-    const size_t n = sl.size();
-    std::vector<int> rcs(n, LDSR_OK);
-    std::vector<std::string> msgs(n);
+// Jobs 0 .. n-1 on n_threads threads, job i on thread i mod n_threads; inline0: thread 0 is the caller's own.
+// The caller's thread keeps the interrupt callback alive until every worker is done, then joins; the first failed
+// job is reported as "<noun> <ids[i]>: <its message>".
+static int run_jobs(int n, int n_threads, bool inline0, const std::function<int(int)> &job, const char *noun,
+                    const std::vector<int> &ids) {
+    std::vector<int> rcs((size_t)std::max(n, 0), LDSR_OK);
+    std::vector<std::string> msgs(rcs.size());
     std::atomic<int> running{0};
-    auto work = [&](size_t d, bool worker) {
+    auto work = [&](int w, bool worker) {
         if (worker) mark_worker_thread();
-        rcs[d] = slice_run(sl[d]);
-        if (rcs[d]) msgs[d] = thread_error();      // thread-local message of this worker
+        for (int i = w; i < n; i += n_threads) {
+            rcs[(size_t)i] = job(i);
+            if (rcs[(size_t)i]) msgs[(size_t)i] = thread_error();      // thread-local message of this thread
+        }
         if (worker) running.fetch_sub(1);
     };
     std::vector<std::thread> pool;
-    for (size_t d = 1; d < n; d++)
-        if (sl[d].n_series > 0) {
-            running.fetch_add(1);
-            pool.emplace_back(work, d, true);
-        }
-    if (n > 0 && sl[0].n_series > 0) work(0, false);
-    while (thread_polls() && running.load() > 0) {     // keep the interrupt callback alive while joining
+    for (int w = inline0 ? 1 : 0; w < n_threads; w++) {
+        running.fetch_add(1);
+        pool.emplace_back(work, w, true);
+    }
+    if (inline0 && n_threads > 0) work(0, false);
+    while (thread_polls() && running.load() > 0) {
         intr_poll();
         usleep(200);
     }
     for (auto &t : pool) t.join();
     if (intr_raised()) return fail(LDSR_EINTERRUPTED, "interrupted by the caller's interrupt callback");
-    for (size_t d = 0; d < n; d++)
-        if (rcs[d]) return fail(rcs[d], "device " + std::to_string(sl[d].device) + ": " + msgs[d]);
+    for (int i = 0; i < n; i++)
+        if (rcs[(size_t)i])
+            return fail(rcs[(size_t)i], noun + std::to_string(ids[(size_t)i]) + ": " + msgs[(size_t)i]);
     return LDSR_OK;
+}
+
+// every slice at once: slice 0 on the caller's thread, one worker per further slice that has cells
+static int run_slices(std::vector<Slice> &sl, const std::function<int(Slice &)> &run) {
+    std::vector<Slice *> live;
+    std::vector<int> devs;
+    for (Slice &S : sl)
+        if (&S == &sl[0] || S.n_cells > 0) { live.push_back(&S); devs.push_back(S.device); }
+    const int n = (int)live.size();
+    return run_jobs(n, n, true, [&](int i) { return run(*live[(size_t)i]); }, "device ", devs);
 }
 
 extern "C" int ldsr_em_batch_multi(int n_devices, const int *devices, int n_series, int T, int p,
@@ -435,10 +483,11 @@ extern "C" int ldsr_em_batch_multi(int n_devices, const int *devices, int n_seri
     if (!theta0 || !theta || !lik || !n_iter || !status) return fail(LDSR_EINVAL, "NULL pointer");
     if (cell_offsets[n_series] == 0) return LDSR_OK;
     IntrScope intr;
+    const GridCall G{n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta0, niter, tol, algo,
+                     theta, lik, n_iter, status, liks};
     std::vector<Slice> sl;
-    make_slices(sl, n_devices, devices, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta0,
-                niter, tol, algo, theta, lik, n_iter, status, liks);
-    return run_slices(sl);
+    make_slices(sl, G, n_devices, devices);
+    return run_slices(sl, slice_run);
 }
 
 extern "C" int ldsr_em_batch(int device, int n_series, int T, int p, int q, const double *y,
@@ -464,100 +513,62 @@ extern "C" int ldsr_em_restart_grid(int n_devices, const int *devices, int n_ser
     if (rc) return rc;
     if (!theta0 || !winner || !theta_w || !lik_w || !n_iter_w)
         return fail(LDSR_EINVAL, "theta0, winner, theta_w, lik_w and n_iter_w must not be NULL");
-    const int n_cells = cell_offsets[n_series];
-    const int P = 6 + p + q;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const int n_cells = cell_offsets[n_series], P = 6 + p + q;
     IntrScope intr;
     if (n_devices > n_cells) n_devices = n_cells > 0 ? n_cells : 1;
-    // One slice: selection and the winners' fit are fused behind the EM kernel on the device and
-    // the per-cell arrays cross PCIe only if asked for.  Several slices: per-cell results come
-    // back first (temporaries if the caller did not ask), the host selects, then phase 2 runs on
-    // the slice that owns each winner.
+    // One slice that can keep its traces selects on the device (slice_restart), and the per-cell arrays cross
+    // PCIe only if asked for.  Anything else brings the per-cell results back first (to temporaries if the caller
+    // did not ask) and selects here.  The winners' phase after the selection is the same.
     const bool want_all = theta_all || lik_all || n_iter_all || status_all;
-    const bool fused = n_devices == 1 && n_cells > 0 &&
-                       sizeof(double) * (size_t)n_cells * niter <= liks_trace_cap_bytes();
+    const bool select_on_device = n_devices == 1 && n_cells > 0 && trace_fits(n_cells, niter);
     std::vector<double> t_theta, t_lik;
     std::vector<int> t_nit, t_st;
-    if (!fused || want_all) {
+    if (!select_on_device || want_all) {
         if (!theta_all) { t_theta.resize((size_t)n_cells * P + 1); theta_all = t_theta.data(); }
         if (!lik_all) { t_lik.resize((size_t)n_cells + 1); lik_all = t_lik.data(); }
         if (!n_iter_all) { t_nit.resize((size_t)n_cells + 1); n_iter_all = t_nit.data(); }
         if (!status_all) { t_st.resize((size_t)n_cells + 1); status_all = t_st.data(); }
     }
+    const GridCall G{n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta0, niter, tol, algo,
+                     theta_all, lik_all, n_iter_all, status_all, nullptr};
+    const WinnerOut out{winner, theta_w, lik_w, n_iter_w, liks_w, X, Y, V, J};
     std::vector<Slice> sl;
-    make_slices(sl, n_devices, devices, n_series, T, p, q, y, u, v, shared_uv, cell_offsets, theta0,
-                niter, tol, algo, theta_all, lik_all, n_iter_all, status_all, nullptr);
+    make_slices(sl, G, n_devices, devices);
     for (Slice &S : sl) S.max_winners = S.n_series;
-    if (fused) {
-        Slice &S = sl[0];
-        S.fuse = true;
-        S.want_all = want_all;
-        S.h_winner = winner; S.h_theta_w = theta_w; S.h_lik_w = lik_w; S.h_nit_w = n_iter_w;
-        S.h_liks_w = liks_w; S.h_X = X; S.h_Y = Y; S.h_V = V; S.h_J = J;
-    }
+    if (select_on_device) return run_slices(sl, [&](Slice &S) { return slice_restart(S, out); });
     if (n_cells > 0) {
-        rc = run_slices(sl);
+        rc = run_slices(sl, slice_run);
         if (rc) return rc;
-        if (fused) {
-            if (!sl[0].fused_done) return fail(LDSR_EINVAL, "internal: fused restart path did not run");
-            return LDSR_OK;     // winner[] is already global (one slice: lo = 0)
-        }
     }
-    // selection (R/LDS_reconstruction.R:50-58), per series over its restarts
+    // selection (R/LDS_reconstruction.R:50-58), per series over its restarts, and what it read of the winner
     for (int s = 0; s < n_series; s++) {
         const int a = cell_offsets[s], b = cell_offsets[s + 1];
         const int k = ldsr_select_restart(b - a, lik_all + a, theta_all + (size_t)a * P, p, q);
-        winner[s] = k < 0 ? -1 : a + k;
         if (k < 0) {
-            for (int j = 0; j < P; j++) theta_w[(size_t)s * P + j] = nan;
-            lik_w[s] = nan;
-            n_iter_w[s] = 0;
-        } else {
-            memcpy(theta_w + (size_t)s * P, theta_all + (size_t)(a + k) * P, sizeof(double) * P);
-            lik_w[s] = lik_all[a + k];
-            n_iter_w[s] = n_iter_all[a + k];
+            fill_no_winner(G, out, s);
+            continue;
         }
-        if (k < 0) {
-            if (liks_w) for (int i = 0; i < niter; i++) liks_w[(size_t)s * niter + i] = nan;
-            double *rows[4] = {X, Y, V, J};
-            for (double *r : rows)
-                if (r) for (int t = 0; t < T; t++) r[(size_t)s * T + t] = nan;
-        }
+        winner[s] = a + k;
+        memcpy(theta_w + (size_t)s * P, theta_all + (size_t)(a + k) * P, sizeof(double) * P);
+        lik_w[s] = lik_all[a + k];
+        n_iter_w[s] = n_iter_all[a + k];
     }
-    if (!liks_w && !X && !Y && !V && !J) return LDSR_OK;
-    // phase 2 on the slice that owns each winner
-    for (size_t d = 0; d < sl.size(); d++) {
-        Slice &S = sl[d];
-        if (S.n_series == 0) continue;
-        std::vector<int> ws_, wc_, gs_;
+    if (!liks_w && !out.want_fit()) return LDSR_OK;     // nothing more is wanted: no device work, no wait
+    // the winners' phase on the slice that owns each winner, one slice after the other
+    for (Slice &S : sl) {
+        std::vector<int> rows, cells;
         for (int s = 0; s < S.n_series; s++) {
             const int lo = S.g_lo[(size_t)s], nc = S.off[(size_t)s + 1] - S.off[(size_t)s];
             if (winner[s] >= lo && winner[s] < lo + nc) {
-                ws_.push_back(s);
-                wc_.push_back(S.off[(size_t)s] + winner[s] - lo);
-                gs_.push_back(s);
+                rows.push_back(s);
+                cells.push_back(S.off[(size_t)s] + winner[s] - lo);
             }
         }
-        const int n_w = (int)ws_.size();
-        if (!n_w) continue;
-        std::vector<double> b_liks, b_X, b_Y, b_V, b_J;
-        if (liks_w) b_liks.resize((size_t)n_w * niter);
-        if (X) b_X.resize((size_t)n_w * T);
-        if (Y) b_Y.resize((size_t)n_w * T);
-        if (V) b_V.resize((size_t)n_w * T);
-        if (J) b_J.resize((size_t)n_w * T);
-        rc = slice_fit_winners(S, n_w, ws_.data(), wc_.data(), liks_w ? b_liks.data() : nullptr,
-                               X ? b_X.data() : nullptr, Y ? b_Y.data() : nullptr,
-                               V ? b_V.data() : nullptr, J ? b_J.data() : nullptr);
+        if (rows.empty()) continue;
+        rc = winners_enqueue(S, rows, cells.data(), out);
         if (rc) return rc;
-        for (int i = 0; i < n_w; i++) {
-            const size_t s = (size_t)gs_[(size_t)i];
-            if (liks_w) memcpy(liks_w + s * niter, b_liks.data() + (size_t)i * niter, sizeof(double) * niter);
-            if (X) memcpy(X + s * T, b_X.data() + (size_t)i * T, sizeof(double) * T);
-            if (Y) memcpy(Y + s * T, b_Y.data() + (size_t)i * T, sizeof(double) * T);
-            if (V) memcpy(V + s * T, b_V.data() + (size_t)i * T, sizeof(double) * T);
-            if (J) memcpy(J + s * T, b_J.data() + (size_t)i * T, sizeof(double) * T);
-        }
+        HIPCHK(hipStreamSynchronize(S.lease.a->stream));
+        winners_deliver(S, rows, out);
     }
     return LDSR_OK;
 }
@@ -566,9 +577,7 @@ extern "C" int ldsr_em_restart_groups(int n_devices, const int *devices, int n_g
                                       ldsr_group *groups, int niter, double tol, int algo) {
     if (n_devices < 1 || !devices) return fail(LDSR_EINVAL, "n_devices must be >= 1");
     if (n_groups < 0 || (n_groups > 0 && !groups)) return fail(LDSR_EINVAL, "groups must not be NULL");
-    std::vector<std::string> msgs((size_t)n_groups);
     IntrScope intr;
-    std::atomic<int> running{0};
     auto work = [&](int g) {
         ldsr_group &G = groups[g];
         // rotate the device list so that concurrent groups start on different GPUs
@@ -578,28 +587,12 @@ extern "C" int ldsr_em_restart_groups(int n_devices, const int *devices, int n_g
                                     G.shared_uv, G.cell_offsets, G.theta0, niter, tol, algo,
                                     G.theta_all, G.lik_all, G.n_iter_all, G.status_all, G.winner,
                                     G.theta_w, G.lik_w, G.n_iter_w, G.liks_w, G.X, G.Y, G.V, G.J);
-        if (G.rc) msgs[(size_t)g] = thread_error();
+        return G.rc;
     };
     // a bounded pool: at most 8 groups in flight (each holds one arena per device)
-    const int n_workers = std::min(n_groups, 8);
-    std::vector<std::thread> pool;
-    for (int w = 0; w < n_workers; w++) {
-        running.fetch_add(1);
-        pool.emplace_back([&, w]() {
-            mark_worker_thread();
-            for (int g = w; g < n_groups; g += n_workers) work(g);
-            running.fetch_sub(1);
-        });
-    }
-    while (thread_polls() && running.load() > 0) {     // the caller's thread keeps the interrupt callback alive
-        intr_poll();
-        usleep(200);
-    }
-    for (auto &t : pool) t.join();
-    if (intr_raised()) return fail(LDSR_EINTERRUPTED, "interrupted by the caller's interrupt callback");
-    for (int g = 0; g < n_groups; g++)
-        if (groups[g].rc) return fail(groups[g].rc, "group " + std::to_string(g) + ": " + msgs[(size_t)g]);
-    return LDSR_OK;
+    std::vector<int> ids((size_t)n_groups);
+    std::iota(ids.begin(), ids.end(), 0);
+    return run_jobs(n_groups, std::min(n_groups, 8), false, work, "group ", ids);
 }
 
 // R/LDS_reconstruction.R:50-58: best lik among models with C > 0 (NaN ignored); if no

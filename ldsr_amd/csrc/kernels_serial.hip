@@ -748,8 +748,9 @@ __global__ __launch_bounds__(64) void mstep_kernel(SmoothParams prm) {
     }
 
 // ---------------------------------------------------------------------------------------
-// gather_winners_kernel: one block per winner; copies its theta / theta0 rows and its
-// likelihood trace (NaN padded beyond n_iter) into the compact winner arrays.
+// gather_winners_kernel: one block per winner; copies its theta / theta0 rows, its lik and
+// n_iter and its likelihood trace (NaN padded beyond n_iter) into the compact winner arrays,
+// and writes its block of the winners' FIT launch.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(128) void gather_winners_kernel(GatherParams prm) {
     const int i = blockIdx.x;
@@ -765,13 +766,11 @@ __global__ __launch_bounds__(128) void gather_winners_kernel(GatherParams prm) {
             prm.liks_w[(long)i * prm.niter + k] = k < n ? prm.liks[c * prm.niter + k] : NAN;
     }
     if (threadIdx.x == 0) {
-        if (prm.lik_w) prm.lik_w[i] = has ? prm.lik[c] : NAN;
-        if (prm.n_iter_w) prm.n_iter_w[i] = has ? prm.n_iter[c] : 0;
-        if (prm.blk) {
-            prm.blk[i] = i;                          // series of the block
-            prm.blk[prm.n_w + i] = i;                // its first cell: row i of the winner arrays
-            prm.blk[2 * prm.n_w + i] = has ? 1 : 0;  // no winner: the block has nothing to do
-        }
+        prm.lik_w[i] = has ? prm.lik[c] : NAN;
+        prm.n_iter_w[i] = has ? prm.n_iter[c] : 0;
+        prm.blk[i] = prm.ser ? prm.ser[i] : i;   // series of the block
+        prm.blk[prm.n_w + i] = i;                // its first cell: row i of the winner arrays
+        prm.blk[2 * prm.n_w + i] = has ? 1 : 0;  // no winner: the block has nothing to do
     }
 }
 

@@ -56,21 +56,22 @@ struct SelectParams {
 };
 
 // Winner extraction of the restart-grid entry: row i of the *_w arrays = cell[i] of the batch
-// (cell[i] < 0: no winner -- NaN rows).  Optionally emits the FIT launch's block table
-// (series i, cell i, one cell or none) and the winners' lik / n_iter.
+// (cell[i] < 0: no winner -- NaN rows), and the FIT launch's block table, one winner per block
+// (its series, cell i, one cell or none).
 struct GatherParams {
     int n_w, P, niter;
     const int *cell;          // [n_w] cell index of each winner, or -1
+    const int *ser;           // [n_w] series of each winner, or null: winner i is series i's
     const double *theta;      // [n_cells][P] fitted
     const double *theta0;     // [n_cells][P] initial
+    const double *lik;        // [n_cells]
     const int *n_iter;        // [n_cells]
     const double *liks;       // [n_cells][niter] traces (entries beyond n_iter undefined), or null
     double *theta_w, *theta0_w;   // [n_w][P]
     double *liks_w;           // [n_w][niter], NaN padded (untouched when liks is null)
-    const double *lik;        // [n_cells] (with lik_w)
-    double *lik_w;            // [n_w] or null
-    int *n_iter_w;            // [n_w] or null
-    int *blk;                 // [3][n_w] block table (series, first cell, cells) or null
+    double *lik_w;            // [n_w]
+    int *n_iter_w;            // [n_w]
+    int *blk;                 // [3][n_w] block table (series, first cell, cells)
 };
 
 static inline int ldsr_pad_dim(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : 16; }

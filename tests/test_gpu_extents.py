@@ -507,6 +507,7 @@ def run_host_entries(path):
                                            return_liks=True))
         keep("grid." + tag, E.em_restart_grid(Y, u0, v0, thg, cell_offsets=off, niter=niter, tol=tol))
         keep("grid_noall." + tag, E.em_restart_grid(Y, U, V, th0, cell_offsets=off, niter=niter, tol=tol, return_all=False))
+        keep("grid_multi." + tag, E.em_restart_grid(Y, U, V, thg, cell_offsets=off, niter=niter, tol=tol, devices=[0, 0, 0]))
     _, U3, V3 = series(130, 3, 3, 3, "ragged")
     keep("groups", E.ensemble_restart(Y, [(u0, v0), (U3[0], V3[0])],
                                       [th0, synth.make_init_packed(3, 3, 11, seed=10)], niter=6, tol=0.0,

@@ -67,38 +67,97 @@ def test_restart_grid_equals_batch_plus_host_logic(eng, devices, tol):
     assert parity_close(fit["lik"], r["lik"], 1e-9, 1e-12)   # the fit is the winner's last E-step
 
 
-def test_restart_grid_without_per_cell_outputs_and_optional_rows(eng):
+@pytest.mark.parametrize("devices", [(0,), (0, 0, 0)])
+def test_restart_grid_without_per_cell_outputs_and_optional_rows(eng, devices):
     Y, u, v, off, th0, p, q = _cv_like(F=3, R=6)
-    full = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5)
-    slim = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5, return_all=False)
+    full = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5, devices=devices)
+    slim = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5, devices=devices,
+                               return_all=False)
     assert "all" not in slim
     for k in ("winner", "theta", "lik", "n_iter", "X", "Y", "V", "J"):
         assert np.array_equal(full[k], slim[k]), k
     assert np.array_equal(full["liks"], slim["liks"], equal_nan=True)
 
 
-def test_restart_grid_winner_rerun_path_is_identical(eng, monkeypatch):
+def _grid_abi_call(Y, u, v, off, th0, p, q, niter, tol, devices, want):
+    """ldsr_em_restart_grid called directly, no per-cell outputs: of liks_w / X / Y / V / J only those named in
+    `want` are passed, the others are NULL.  The outputs start from a sentinel no result can hold."""
+    from ldsr_amd import _lib
+    from ldsr_amd.api import _d, _i
+    S, T = Y.shape
+    P = 6 + p + q
+    U, V = np.ascontiguousarray(u.T), np.ascontiguousarray(v.T)
+    devs = np.asarray(devices, dtype=np.int32)
+    out = {"winner": np.full(S, -77, np.int32), "theta": np.full((S, P), -77.0), "lik": np.full(S, -77.0),
+           "n_iter": np.full(S, -77, np.int32)}
+    shapes = {"liks": (S, niter), "X": (S, T), "Y": (S, T), "V": (S, T), "J": (S, T)}
+    for k in want:
+        out[k] = np.full(shapes[k], -77.0)
+    _lib.check(_lib.lib().ldsr_em_restart_grid(
+        devs.size, _i(devs), S, T, p, q, _d(Y), _d(U), _d(V), 1, _i(off), _d(th0), niter, tol, 0,
+        None, None, None, None, _i(out["winner"]), _d(out["theta"]), _d(out["lik"]), _i(out["n_iter"]),
+        _d(out.get("liks")), _d(out.get("X")), _d(out.get("Y")), _d(out.get("V")), _d(out.get("J"))))
+    return out
+
+
+@pytest.mark.parametrize("devices", [(0,), (0, 0, 0)])
+def test_restart_grid_abi_null_optional_outputs(eng, devices):
+    """The header allows NULL for any of liks_w / X / Y / V / J: what is given equals the full call's."""
+    Y, u, v, off, th0, p, q = _cv_like(F=3, R=6)
+    th0 = np.ascontiguousarray(th0)
+    full = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5, devices=devices)
+    some = _grid_abi_call(Y, u, v, off, th0, p, q, 40, 1e-5, devices, want=("Y", "J"))
+    none = _grid_abi_call(Y, u, v, off, th0, p, q, 40, 1e-5, devices, want=())
+    for k in ("winner", "theta", "lik", "n_iter"):
+        assert np.array_equal(some[k], full[k]), k
+        assert np.array_equal(none[k], full[k]), k
+    for k in ("Y", "J"):
+        assert np.array_equal(some[k], full[k]), k
+
+
+@pytest.mark.parametrize("devices", [(0,), (0, 0, 0)])
+def test_restart_grid_winner_rerun_path_is_identical(eng, monkeypatch, devices):
     """Traces too large to keep on the device (cap forced to 0): the winners are re-run alone."""
     Y, u, v, off, th0, p, q = _cv_like()
-    a = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=80, tol=1e-5)
+    a = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=80, tol=1e-5, devices=devices)
     monkeypatch.setenv("LDSR_LIKS_TRACE_MAX_BYTES", "0")
-    b = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=80, tol=1e-5)
+    b = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=80, tol=1e-5, devices=devices)
     for k in ("winner", "theta", "lik", "n_iter", "X", "Y", "V", "J"):
         assert np.array_equal(a[k], b[k]), k
     assert np.array_equal(a["liks"], b["liks"], equal_nan=True)
 
 
-def test_restart_grid_series_without_a_selectable_winner(eng):
+@pytest.mark.parametrize("devices", [(0,), (0, 0, 0)])
+def test_restart_grid_series_without_a_selectable_winner(eng, devices):
     """A fold whose restarts all end with NaN likelihoods has no winner (R's which.max on
     all-NA gives integer(0)): winner -1 and NaN rows, the other folds are unaffected."""
     Y, u, v, off, th0, p, q = _cv_like(F=3, R=4)
     th0 = th0.copy()
     th0[off[1]:off[2], 0] = np.nan               # NaN A in every restart of fold 1: NaN likelihoods throughout
-    r = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=3, tol=0.0)
+    r = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=3, tol=0.0, devices=devices)
     assert np.all(np.isnan(r["all"]["lik"][off[1]:off[2]]))
     assert r["winner"][1] == -1 and r["winner"][0] >= 0 and r["winner"][2] >= 0
     assert np.all(np.isnan(r["theta"][1])) and np.all(np.isnan(r["X"][1])) and np.all(np.isnan(r["liks"][1]))
     assert np.all(np.isfinite(r["X"][[0, 2]]))
+
+
+def _same_grid_result(a, b):
+    for k in ("winner", "theta", "lik", "n_iter", "liks", "X", "Y", "V", "J"):
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    for k in ("theta", "lik", "n_iter", "status"):
+        assert np.array_equal(a["all"][k], b["all"][k], equal_nan=True), k
+
+
+def test_restart_grid_fewer_restarts_than_slices(eng):
+    """Two restarts per series over three slices: every series has an empty part on one slice; and one series
+    with two restarts, where the entry runs two slices instead of three."""
+    Y, u, v, off, th0, p, q = _cv_like(F=3, R=2)
+    one = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5, devices=(0,))
+    three = eng.em_restart_grid(Y, u, v, th0, cell_offsets=off, niter=40, tol=1e-5, devices=(0, 0, 0))
+    _same_grid_result(three, one)
+    one = eng.em_restart_grid(Y[0], u, v, th0[:2], niter=40, tol=1e-5, devices=(0,))
+    three = eng.em_restart_grid(Y[0], u, v, th0[:2], niter=40, tol=1e-5, devices=(0, 0, 0))
+    _same_grid_result(three, one)
 
 
 def test_lds_em_restart_matches_oracle_winner(eng, p1case):
